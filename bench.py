@@ -8,7 +8,11 @@ rank (ManualTrainer.manual_training_step) + gradient exchange + fused AdamW
 (manual_optimization_step), exactly the unit `estimate_step_time` extrapolates
 (src/benchmarking/step_time.py:75-97) — here measured directly, synchronized.
 
-Usage: python bench.py [--gpus N --steps K --warmup W --micro-batch M]
+Usage: python bench.py [--gpus N --steps K --warmup W --micro-batch M] [--full]
+                       [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the
+measurements the headline figure does not need (the 8192^3 GEMM yardstick, the CPU
+baseline); `--dump-outputs DIR` writes the last timed step's outputs as DIR/<name>.npy.
 Multi-GPU: `python bench.py --gpus N` starts its N ranks itself (one process per GPU through
 torch.distributed.run, before any GPU call — the reference's launcher does the same,
 experiments/utils/distribute.py:37-61), or run it under
@@ -70,6 +74,14 @@ def parse():
                     help="stage one set of micro-batches before the timed region and reuse it "
                          "every step (round-2 mode) instead of a fresh batch per step")
     ap.add_argument("--no-yardstick", action="store_true", help="skip the 8192^3 GEMM yardstick")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the 8192^3 GEMM "
+                         "yardstick before the timed region and the CPU baseline after it "
+                         "(--no-yardstick / --no-cpu-baseline / --no-cpu-variants trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned and "
+                         "left behind (loss, a fixed seeded sample of the updated parameters) "
+                         "as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -353,6 +365,34 @@ def probe_micro_batch(trainer, cfg, per_rank: int, text_len: int, device, world:
     return best
 
 
+DUMP_SAMPLE = 1 << 22  # elements per sampled buffer: 2 x 16 MiB of float32, below 64 MB
+
+
+def dump_outputs(dirname: str, trainer, loss, n_items: int, world: int) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64
+    `.npy` files (rank 0's view): `loss_sum` (train_step's return value, the step's CE sum on
+    this rank), `loss` (per label token, as the line reports it; one GPU only), and the state
+    the step left for the next one at a fixed, seeded sample of flat-buffer positions:
+    `master_sample` (fp32 master weights this rank holds on the device) and `shadow_sample`
+    (the bf16 weights the next forward reads).  Inputs and initial weights are seeded, so two
+    builds run with the same arguments can be compared file by file."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "loss_sum.npy"), loss.detach().float().cpu().numpy())
+    if world == 1:
+        np.save(os.path.join(dirname, "loss.npy"),
+                np.array([loss.item() / n_items], dtype=np.float64))
+    for name, buf in (("master_sample", trainer.store.master),
+                      ("shadow_sample", trainer.store.shadow)):
+        n = buf.numel()
+        if n > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(20260)
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+            buf = buf[idx.to(buf.device)]
+        np.save(os.path.join(dirname, name + ".npy"), buf.detach().float().cpu().numpy())
+
+
 def _free_port() -> int:
     import socket
 
@@ -589,7 +629,7 @@ def main():
         one_step()
     trainer.flush()
     torch.cuda.synchronize()
-    yard = None if args.no_yardstick else gemm_yardstick(device)
+    yard = gemm_yardstick(device) if args.full and not args.no_yardstick else None
     if world > 1:
         dist.barrier()
     clock = ClockSampler(local)
@@ -630,6 +670,8 @@ def main():
     probe = K.stop_gemm_probe()
     if loader is not None:
         loader.close()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss, n_items, world)
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -758,7 +800,7 @@ def main():
         "roofline": roofline,
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args.model, args.text_len, args.cpu_budget_s,
                                                not args.no_cpu_variants)

@@ -14,5 +14,5 @@ cat $OUT/attn_a.jsonl
 timeout -k 10 300 env $BARM python -u scripts/bench_attn.py > $OUT/attn_b.jsonl 2> $OUT/attn_b.err || { tail -20 $OUT/attn_b.err; exit 1; }
 cat $OUT/attn_b.jsonl
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o run -- python3 scripts/bench_attn.py --iters 5 > $OUT/trace.jsonl 2> $OUT/trace.err || { tail -20 $OUT/trace.err; exit 1; }
-timeout -k 10 400 python -u bench.py --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json

@@ -5,7 +5,7 @@
 # Usage: bash scripts/diag/gpu.sh <tag> <step> [<step> ...]      (output: gpurun_out/<tag>/)
 #   tests[=<-k expr>]        pytest -m gpu (all files, or `-k expr`), verbose log
 #   smoke                    __graft_entry__.smoke()
-#   bench[=<args>]           default bench line (+ args; commas -> spaces), bench_<n>.json
+#   bench[=<args>]           default bench line with --full (+ args; commas -> spaces), bench_<n>.json
 #   trace[=<args>]           rocprofv3 kernel trace of a bench run + prof_vs_line check
 #   pmc=<counters>[@<args>]  one rocprofv3 --pmc pass (commas -> spaces) over a bench run
 #   traffic                  FETCH_SIZE and WRITE_SIZE passes (GEMM kernels) over the bench
@@ -42,7 +42,7 @@ for step in "$@"; do
       tail -1 "$OUT/smoke.log" ;;
     bench)
       nb=$((nb+1))
-      timeout -k 10 600 python -u bench.py ${arg//,/ } > "$OUT/bench_$nb.json" 2> "$OUT/bench_$nb.err" \
+      timeout -k 10 600 python -u bench.py --full ${arg//,/ } > "$OUT/bench_$nb.json" 2> "$OUT/bench_$nb.err" \
           || { tail -20 "$OUT/bench_$nb.err"; exit 1; }
       last_json "$OUT/bench_$nb.json" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d.get('roofline') or {}; print('bench', d['value'], d['ms_per_step'], (d.get('clock') or {}).get('median_mhz'), (d.get('gemm_yardstick') or {}).get('tflops'), r.get('frac'), r.get('gemm_compute_stream_tflops'))" ;;
     trace)

@@ -6,7 +6,7 @@ OUT=gpurun_out/configs
 mkdir -p "$OUT"
 run() {
   local tag=$1; shift
-  timeout -k 10 500 python -u bench.py --no-cpu-baseline "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.err" \
+  timeout -k 10 500 python -u bench.py --full --no-cpu-baseline "$@" > "$OUT/$tag.json" 2> "$OUT/$tag.err" \
       || { tail -20 "$OUT/$tag.err"; exit 1; }
   python -c "import json;d=json.load(open('$OUT/$tag.json'));print('$tag',d['value'],d['ms_per_step'],d['mfu'],d['loss'],d['max_memory_reserved_gb'])"
 }

@@ -11,7 +11,7 @@ tail -3 "$OUT/pytest.log"
 i=0
 for B in "$@"; do
   i=$((i+1))
-  timeout -k 10 400 python -u bench.py --no-cpu-baseline $B > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err" \
+  timeout -k 10 400 python -u bench.py --full --no-cpu-baseline $B > "$OUT/bench_$i.json" 2> "$OUT/bench_$i.err" \
       || { tail -20 "$OUT/bench_$i.err"; exit 1; }
   cat "$OUT/bench_$i.json"
 done

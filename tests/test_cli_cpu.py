@@ -174,3 +174,64 @@ def test_visible_gpus_counts_from_sysfs_without_hip(tmp_path):
     src = open(os.path.join(ROOT, "bench.py")).read()
     body = src[src.index("def self_launch"):src.index("def launch_check")]
     assert "torch.cuda" not in body
+
+
+def _load_bench():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_is_lean_and_full_is_an_option(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` asks for neither the GEMM yardstick
+    nor the CPU baseline; `--full` switches both on, and `--dump-outputs` takes a folder."""
+    import sys
+
+    bench = _load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs == ""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    main = src[src.index("def main"):]
+    for call in ("gemm_yardstick(", "cpu_baseline("):  # every use in main() is behind --full
+        for line in main.splitlines():
+            if call in line:
+                at = main.index(line)
+                assert "args.full" in main[max(0, at - 200):at + len(line)], line
+
+
+def test_bench_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: the last step's loss and a fixed, seeded sample of the weights it left,
+    float32 / float64 `.npy`, the same positions on every call, at most 64 MB in all."""
+    import types
+
+    import numpy as np
+    import torch
+
+    bench = _load_bench()
+    n = bench.DUMP_SAMPLE + 1000
+    master = torch.arange(n, dtype=torch.float32)
+    store = types.SimpleNamespace(master=master, shadow=torch.ones(64, dtype=torch.bfloat16))
+    trainer = types.SimpleNamespace(store=store)
+    loss = torch.tensor([12.5])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), trainer, loss, 5, 1)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["loss.npy", "loss_sum.npy", "master_sample.npy", "shadow_sample.npy"]
+    total = 0
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+        total += x.nbytes
+    assert total <= 64 * 2**20
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == 2.5
+    assert np.load(tmp_path / "a" / "loss_sum.npy")[0] == 12.5
+    m = np.load(tmp_path / "a" / "master_sample.npy")
+    assert m.shape == (bench.DUMP_SAMPLE,) and (np.diff(m) >= 0).all() and m.max() < n
+    assert np.load(tmp_path / "a" / "shadow_sample.npy").shape == (64,)

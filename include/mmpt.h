@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MMPT_ABI_VERSION 14
+#define MMPT_ABI_VERSION 15
 
 enum mmpt_status { MMPT_OK = 0, MMPT_ERR_ARG = -1, MMPT_ERR_UNSUPPORTED = -2 };
 
@@ -211,6 +211,14 @@ int mmpt_rope_inplace(int64_t tokens, int64_t seq, int64_t heads, int64_t head_d
                       int64_t rot_dims, void* qkv, int64_t ld, int64_t head_stride,
                       int64_t part_stride, int64_t parts, const float* cos, const float* sin,
                       int inverse, void* stream);
+/* ABI 15: the same rotation with the table row of token t read from pos[t] (device int32,
+ * 0 <= pos[t] < table_rows: the caller's contract) instead of t % seq — the positions of an
+ * unpadded batch, where sequence b is rows [cu[b], cu[b+1]) and pos restarts at 0 in each.
+ * The arithmetic is mmpt_rope_inplace's: with pos[t] = t % seq the results are bitwise equal. */
+int mmpt_rope_inplace_pos(int64_t tokens, int64_t heads, int64_t head_dim, int64_t rot_dims,
+                          void* qkv, int64_t ld, int64_t head_stride, int64_t part_stride,
+                          int64_t parts, const float* cos, const float* sin, int64_t table_rows,
+                          const int32_t* pos, int inverse, void* stream);
 
 /* ------------------------------------------------------------------------
  * K2/K3  scaled-dot-product attention (torch SDPA, causal for GPTNeoX
@@ -257,6 +265,32 @@ int mmpt_attention_gqa_bwd(int64_t batch, int64_t seq, int64_t heads, int64_t kv
                            int64_t k_offset, int64_t v_offset, int causal, float scale,
                            const void* out, const void* dout, int64_t ld_out, const float* lse,
                            void* dqkv, void* workspace, void* stream);
+/* ABI 15  variable-length (unpadded) batches, the flash-attention varlen form: the token rows
+ * of `batch` sequences are packed back to back, sequence b being rows [cu_seqlens[b],
+ * cu_seqlens[b+1]) of qkv / out / dout / dqkv (total_tokens rows each).  cu_seqlens: device
+ * int32 [batch + 1], ascending, cu[0] = 0, cu[batch] = total_tokens, every length in
+ * [1, max_seq] — its contents are the caller's contract (the entry checks the pointer, max_seq
+ * >= 1, batch <= total_tokens <= batch * max_seq and the 32-bit offset limits only).  Each
+ * sequence is attended on its own, causal or not, and gets bitwise what mmpt_attention_gqa_fwd /
+ * _bwd give for it alone (batch = 1, seq = its length).  lse is fp32 [batch][heads][max_seq];
+ * entries past a sequence's length are left untouched, as is every row past total_tokens.
+ * Layout arguments as mmpt_attention_gqa_*; every head dim of the dense path.  The backward
+ * writes every q, k and v element of every dqkv row once (no atomics); at head_dim 256 it runs
+ * the ring dK/dV and recomputing dQ kernels (what MMPT_ATTN_DS=0 selects for the dense entry),
+ * so its workspace is δ only and the rope backward is a separate mmpt_rope_inplace_pos call. */
+int mmpt_attention_varlen_fwd(int64_t batch, int64_t max_seq, int64_t total_tokens, int64_t heads,
+                              int64_t kv_heads, int64_t head_dim, const void* qkv, int64_t ld,
+                              int64_t head_stride, int64_t k_offset, int64_t v_offset, int causal,
+                              float scale, const int32_t* cu_seqlens, void* out, int64_t ld_out,
+                              float* lse, void* stream);
+int64_t mmpt_attention_varlen_bwd_workspace_bytes(int64_t batch, int64_t max_seq, int64_t heads,
+                                                  int64_t head_dim);
+int mmpt_attention_varlen_bwd(int64_t batch, int64_t max_seq, int64_t total_tokens, int64_t heads,
+                              int64_t kv_heads, int64_t head_dim, const void* qkv, int64_t ld,
+                              int64_t head_stride, int64_t k_offset, int64_t v_offset, int causal,
+                              float scale, const int32_t* cu_seqlens, const void* out,
+                              const void* dout, int64_t ld_out, const float* lse, void* dqkv,
+                              void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------
  * K12  ForCausalLMLoss (tf:loss/loss_utils.py:32-68): fp32 upcast, CE with

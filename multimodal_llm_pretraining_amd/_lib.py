@@ -13,7 +13,7 @@ from ctypes import c_float, c_int, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMPT_LIB") or os.path.join(_HERE, "lib", "libmmpt.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _lib: ctypes.CDLL | None = None
 
@@ -48,6 +48,7 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_layernorm_f32_fwd": (I32, [I64, I64, F32, P, P, P, P, P, P, P]),
     "mmpt_layernorm_f32_bwd": (I32, [I64, I64, P, P, P, P, P, P, P, P, P, P]),
     "mmpt_rope_inplace": (I32, [I64, I64, I64, I64, I64, P, I64, I64, I64, I64, P, P, I32, P]),
+    "mmpt_rope_inplace_pos": (I32, [I64, I64, I64, I64, P, I64, I64, I64, I64, P, P, I64, P, I32, P]),
     "mmpt_rmsnorm_fwd": (I32, [I64, I64, F32, P, I64, P, P, P, P]),
     "mmpt_rmsnorm_bwd_workspace_bytes": (I64, [I64, I64]),
     "mmpt_rmsnorm_bwd": (I32, [I64, I64, P, I64, P, P, P, P, P, P, P, P, P]),
@@ -57,6 +58,9 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_attention_bwd_rope": (I32, [I64, I64, I64, I64, P, I64, I64, I64, I32, F32, P, P, I64, P, P, P, I64, P, P, P]),
     "mmpt_attention_gqa_fwd": (I32, [I64, I64, I64, I64, I64, P, I64, I64, I64, I64, I32, F32, P, I64, P, P]),
     "mmpt_attention_gqa_bwd": (I32, [I64, I64, I64, I64, I64, P, I64, I64, I64, I64, I32, F32, P, P, I64, P, P, P, P]),
+    "mmpt_attention_varlen_fwd": (I32, [I64, I64, I64, I64, I64, I64, P, I64, I64, I64, I64, I32, F32, P, P, I64, P, P]),
+    "mmpt_attention_varlen_bwd_workspace_bytes": (I64, [I64, I64, I64, I64]),
+    "mmpt_attention_varlen_bwd": (I32, [I64, I64, I64, I64, I64, I64, P, I64, I64, I64, I64, I32, F32, P, P, P, I64, P, P, P, P]),
     "mmpt_cross_entropy": (I32, [I64, I64, I64, P, I64, P, I64, F32, P, P, I64, P]),
     "mmpt_sum_workspace_bytes": (I64, [I64]),
     "mmpt_sum_f32": (I32, [I64, P, P, P, P]),

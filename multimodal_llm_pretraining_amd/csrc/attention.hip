@@ -56,7 +56,26 @@ struct AttnParams {
   const float* rcos;
   const float* rsin;
   int rot;  // 0: no rotation
+  // varlen (mmpt_attention_varlen_*, the VL kernel variants): sequence b is rows
+  // [cu[b], cu[b+1]) of qkv / out / dout / dqkv; S is then max_seq — the stride of lse / δ and
+  // the width the work items are enumerated over.  Null on every dense entry point.
+  const int* cu;
 };
+
+// Row geometry of sequence b (wave-uniform b): its length and its first row.  Dense (VL =
+// false): S and b·S, the expressions the dense kernels always used.  VL: from cu, pinned to
+// scalar registers — hipcc cannot prove the load uniform, and the values feed wave-uniform
+// operands (LDS-DMA bases, the m0 LDS address through the buffer parity).
+template <bool VL>
+__device__ __forceinline__ int seq_len(const AttnParams& p, int b) {
+  if constexpr (VL) return __builtin_amdgcn_readfirstlane(p.cu[b + 1] - p.cu[b]);
+  else return p.S;
+}
+template <bool VL>
+__device__ __forceinline__ int seq_row0(const AttnParams& p, int b) {
+  if constexpr (VL) return __builtin_amdgcn_readfirstlane(p.cu[b]);
+  else return b * p.S;
+}
 constexpr int FUSED_ROT = 64;  // the rotary width the fused epilogues handle (Pythia: D / 4)
 
 // The inverse rotary pairs (d, d + 32) of the d-tiles dt = 0, 1 and dt + 2 of an accumulator
@@ -377,7 +396,7 @@ __device__ __forceinline__ int dst_pos(int L) { return L ^ ((L >> 4) & 3); }
 // One workgroup = 4 waves = 64·QT query rows; wave w owns QT 16-row query tiles.
 // K/V blocks of 64 keys are double-buffered in LDS by LDS-DMA (128 KiB at D=256):
 // the DMA of block j+1 is issued before the MFMAs of block j.
-template <int D, bool CAUSAL, int QT, int NW, int DR = D>
+template <int D, bool CAUSAL, int QT, int NW, int DR = D, bool VL = false>
 __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
   using I = Img<D>;
   constexpr int KS = dr_ksteps<D, DR>(), DT = DR / 16;
@@ -392,11 +411,26 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
   constexpr int BQ = NW * 16 * QT;
   const int nx = (p.S + BQ - 1) / BQ;
   const int nitems = nx * p.B * p.H;
+  // varlen: the items are enumerated over max_seq (p.S); one whose query block starts past its
+  // sequence's end is empty.  item_at skips them — position k of this workgroup's item list and
+  // on, to the first non-empty item — so the loop below, its next-item K/V prefetch included,
+  // only ever sees items that have rows (workgroup-uniform: cu is read at uniform indices).
+  auto item_at = [&](int& k) {
+    for (;; ++k) {
+      const int w = attn_item(nitems, k);
+      if (!VL || w < 0) return w;
+      if ((nx - 1 - w % nx) * BQ < seq_len<VL>(p, w / nx / p.H)) return w;
+    }
+  };
   int it = 0;
-  int wid = attn_item(nitems, 0);
+  int wid = item_at(it);
   if (wid < 0) return;  // (workgroup-uniform)
   const float sl2 = p.scale * LOG2E;
   const int nkb_all = (p.S + ABLK - 1) / ABLK;
+  // VL: length and first row of the current item's sequence (dense: p.S and b * p.S)
+  int vsl = 0, vr0 = 0;
+  auto LEN = [&](int v) { return VL ? v : p.S; };
+  auto ROW0 = [&](int v, int bb) { return VL ? v : bb * p.S; };
 
   // per-item state: (query block, batch, head), its Q fragments in registers
   int b, h, bh, q0, nkb;
@@ -413,26 +447,30 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
     q0_ = bx * BQ;
   };
   auto load_q = [&]() {
-    nkb = CAUSAL ? min(nkb_all, (q0 + BQ - 1) / ABLK + 1) : nkb_all;
+    const int nkb_s = VL ? (vsl + ABLK - 1) / ABLK : nkb_all;
+    nkb = CAUSAL ? min(nkb_s, (q0 + BQ - 1) / ABLK + 1) : nkb_s;
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
       myq[qt] = q0 + wave * 16 * QT + qt * 16 + (lane & 15);
-      const bf16_t* qrow = p.qkv + (long)(b * p.S + min(myq[qt], p.S - 1)) * p.ld + h * p.hs;
+      const bf16_t* qrow =
+          p.qkv + (long)(ROW0(vr0, b) + min(myq[qt], LEN(vsl) - 1)) * p.ld + h * p.hs;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) qf[qt][ks] = gfrag_m<D>(qrow, ks, lane, p.dr);
     }
   };
-  // key block kb of (batch bb, k/v columns kc/vc) into LDS buffer `buf`
-  auto stage_kv = [&](int buf, int bb, long kc, long vc, int kb) {
+  // key block kb of (batch bb, k/v columns kc/vc) into LDS buffer `buf` (VL: the sequence's
+  // length ssl and first row sr0)
+  auto stage_kv = [&](int buf, int bb, long kc, long vc, int kb, int ssl, int sr0) {
+    const int S_ = LEN(ssl);
     char* img = smem + buf * 2 * I::BYTES;
     if constexpr (D == 256) {
       // K and V pieces share their per-lane row / chunk offsets (32-bit, from a uniform base
       // at the batch's row 0): ~4 VALU per piece pair instead of ~8 of 64-bit math per piece
       constexpr int PPW = (D / 8) / NW;
-      const char* bk = (const char*)(p.qkv + (long)bb * p.S * p.ld + kc);
+      const char* bk = (const char*)(p.qkv + (VL ? (long)sr0 : (long)bb * p.S) * p.ld + kc);
       const char* bv = bk + (vc - kc) * 2;
       const int ldb = (int)p.ld * 2;
-      if (MMPT_ATTN_SADDR && kb * ABLK + ABLK <= p.S) {
+      if (MMPT_ATTN_SADDR && kb * ABLK + ABLK <= S_) {
         // a whole block: wave-uniform bases at its first key, per-lane 32-bit offsets (SADDR)
         const char* bk0 = bk + kb * ABLK * ldb;
         const char* bv0 = bv + kb * ABLK * ldb;
@@ -452,29 +490,43 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
           const int q = wave * PPW + i;
           int r, lc;
           I::template piece<ABLK>(q, lane, r, lc);
-          const int off = min(kb * ABLK + r, p.S - 1) * ldb + (lc << 4);
+          const int off = min(kb * ABLK + r, S_ - 1) * ldb + (lc << 4);
           glds16(bk + off, img + q * 1024);
           glds16(bv + off, img + I::BYTES + q * 1024);
         }
       }
     } else {
-      I::template dma<NW>(img, p.qkv, p.ld, kc, p.S, bb, kb * ABLK, wave, lane, p.dr);
-      I::template dma<NW>(img + I::BYTES, p.qkv, p.ld, vc, p.S, bb, kb * ABLK, wave, lane, p.dr);
+      const bf16_t* base = VL ? p.qkv + (long)sr0 * p.ld : p.qkv;  // (VL: batch index 0 below)
+      const int bi = VL ? 0 : bb;
+      I::template dma<NW>(img, base, p.ld, kc, S_, bi, kb * ABLK, wave, lane, p.dr);
+      I::template dma<NW>(img + I::BYTES, base, p.ld, vc, S_, bi, kb * ABLK, wave, lane, p.dr);
     }
   };
   decode(wid, b, h, bh, q0, kcol, vcol);
+  if constexpr (VL) {
+    vsl = seq_len<VL>(p, b);
+    vr0 = seq_row0<VL>(p, b);
+  }
   load_q();
-  stage_kv(0, b, kcol, vcol, 0);
+  stage_kv(0, b, kcol, vcol, 0, vsl, vr0);
   int par = 0;  // LDS buffer of the item's key block kb: (kb + par) & 1
   v4f o[QT][DT];
   float m[QT], l[QT];
   for (;;) {
   // the next item: its key block 0 goes out during this item's last key block, into the
   // buffer that block leaves free
-  const int wid_n = attn_item(nitems, it + 1);
+  int itn = it + 1;
+  const int wid_n = item_at(itn);
   int nb = 0, nh = 0, nbh = 0, nq0 = 0;
   long nkc = 0, nvc = 0;
-  if (wid_n >= 0) decode(wid_n, nb, nh, nbh, nq0, nkc, nvc);
+  int nsl = 0, nr0 = 0;
+  if (wid_n >= 0) {
+    decode(wid_n, nb, nh, nbh, nq0, nkc, nvc);
+    if constexpr (VL) {
+      nsl = seq_len<VL>(p, nb);
+      nr0 = seq_row0<VL>(p, nb);
+    }
+  }
   vm_wait_all();
   __syncthreads();
 #pragma unroll
@@ -496,8 +548,8 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
     char* kimg = smem + ((kb + par) & 1) * 2 * I::BYTES;
     char* vimg = kimg + I::BYTES;
     if (MMPT_ATTN_DIAG != 2) {
-      if (kb + 1 < nkb) stage_kv((kb + 1 + par) & 1, b, kcol, vcol, kb + 1);
-      else if (wid_n >= 0) stage_kv((kb + 1 + par) & 1, nb, nkc, nvc, 0);
+      if (kb + 1 < nkb) stage_kv((kb + 1 + par) & 1, b, kcol, vcol, kb + 1, vsl, vr0);
+      else if (wid_n >= 0) stage_kv((kb + 1 + par) & 1, nb, nkc, nvc, 0, nsl, nr0);
     }
     v4f s[QT][4];
 #pragma unroll
@@ -537,7 +589,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
     // ---- online softmax, deferred max (cdna_hip_programming.md T13) ----
     // Raw scores; the mask only on blocks that touch the diagonal or the sequence end
     // (wave-uniform test against this wave's first query row).
-    const bool masked = (k0 + ABLK > p.S) ||
+    const bool masked = (k0 + ABLK > LEN(vsl)) ||
                         (CAUSAL && k0 + ABLK - 1 > q0 + wave * 16 * QT);
     if (masked) {
 #pragma unroll
@@ -547,7 +599,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int key = k0 + kt * 16 + 4 * g + i;
-            if (key >= p.S || (CAUSAL && key > myq[qt])) s[qt][kt][i] = -INFINITY;
+            if (key >= LEN(vsl) || (CAUSAL && key > myq[qt])) s[qt][kt][i] = -INFINITY;
           }
     }
     // m[qt] is the (lane-uniform per row) reference max in log2 units.  Keep it while
@@ -621,21 +673,26 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
     __syncthreads();
   }
   for (int kb = nkb_w; kb < nkb; ++kb) {
-    if (kb + 1 < nkb) stage_kv((kb + 1 + par) & 1, b, kcol, vcol, kb + 1);
-    else if (wid_n >= 0) stage_kv((kb + 1 + par) & 1, nb, nkc, nvc, 0);
+    if (kb + 1 < nkb) stage_kv((kb + 1 + par) & 1, b, kcol, vcol, kb + 1, vsl, vr0);
+    else if (wid_n >= 0) stage_kv((kb + 1 + par) & 1, nb, nkc, nvc, 0, nsl, nr0);
     vm_wait_all();
     __syncthreads();
   }
   // every wave is past the item's last barrier: the LDS buffer of the last key block is
   // free (the next item's block 0 went to the other one) and stages this item's O
   const int cb = b, ch = h, cbh = bh, cq0 = q0 + wave * 16 * QT;
+  const int csl = vsl, cr0 = vr0;
   char* ostage = smem + ((nkb - 1 + par) & 1) * 2 * I::BYTES + wave * (16 * QT * I::RB);
   int cq[QT];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) cq[qt] = myq[qt];
   wid = wid_n;
-  ++it;
+  it = itn;
   if (wid >= 0) {
+    if constexpr (VL) {
+      vsl = nsl;
+      vr0 = nr0;
+    }
     par = (nkb + par) & 1;
     b = nb;
     h = nh;
@@ -668,7 +725,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
       const int c = 2 * dt + (g >> 1);
       stage_w8(ostage + r * I::RB, c ^ (r & SWM), g & 1, r, u);
     }
-    if (g == 0 && cq[qt] < p.S)
+    if (g == 0 && cq[qt] < LEN(csl))
       p.lse[(long)cbh * p.S + cq[qt]] = (m[qt] + log2f(l[qt])) / LOG2E;  // natural log
   }
   {
@@ -677,8 +734,8 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
     for (int i = 0; i < 16 * QT / RPI; ++i) {
       const int r = i * RPI + rr;
       const uint4 v = *(const uint4*)(ostage + r * I::RB + ((c ^ (r & SWM)) << 4));
-      if (cq0 + r < p.S && chunk_real<D>(c, p.dr))
-        *(uint4*)(p.out + (long)(cb * p.S + cq0 + r) * p.ld_out + ch * p.dr + c * 8) = v;
+      if (cq0 + r < LEN(csl) && chunk_real<D>(c, p.dr))
+        *(uint4*)(p.out + (long)(ROW0(cr0, cb) + cq0 + r) * p.ld_out + ch * p.dr + c * 8) = v;
     }
   }
   if (wid < 0) break;
@@ -688,15 +745,34 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
 
 // δ[bh][q] = Σ_d dO·O  (fp32 of bf16 values).  16-B loads: LPR = D/8 lanes per (t, h)
 // row, 64/LPR rows per wave, shuffle-reduced within the row's lanes.
-template <int D>
+// VL: the rows are enumerated over (b, q < max_seq, h); those with q past their sequence's end
+// load and store nothing, the others read token row cu[b] + q.
+template <int D, bool VL = false>
 __global__ __launch_bounds__(256) void attn_delta_kernel(AttnParams p, float* delta) {
   constexpr int LPR = D / 8, RPW = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const long row = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;  // (t, h)
-  const bool ok = row < (long)p.B * p.S * p.H;
+  bool ok = row < (long)p.B * p.S * p.H;
   const long r = ok ? row : 0;
   const int h = (int)(r % p.H);
-  const long t = r / p.H;
+  long t = r / p.H;
+  if constexpr (VL) {
+    const int b = (int)(t / p.S), q = (int)(t % p.S);
+    ok = ok && q < p.cu[b + 1] - p.cu[b];  // (b differs between the lanes of a wave)
+    t = ok ? (long)p.cu[b] + q : 0;
+    float s = 0.f;
+    const int c = (lane % LPR) * 8;
+    if (chunk_real<D>(c / 8, p.dr)) {
+      const v8s o = *(const v8s*)(p.o + t * p.ld_out + h * p.dr + c);
+      const v8s d = *(const v8s*)(p.dout + t * p.ld_out + h * p.dr + c);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s += bf2f((bf16_t)o[e]) * bf2f((bf16_t)d[e]);
+    }
+#pragma unroll
+    for (int off = LPR / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (ok && lane % LPR == 0) delta[((long)b * p.H + h) * p.S + q] = s;
+    return;
+  }
   const int c = (lane % LPR) * 8;
   float s = 0.f;
   if (chunk_real<D>(c / 8, p.dr)) {
@@ -729,12 +805,13 @@ constexpr int dkdv_slots() { return D == 256 ? MMPT_ATTN_DKDV_NS : 4; }
 // workgroups per CU the ring's LDS allows (2 also halves the register budget: KT = 1 only)
 template <int D>
 constexpr int dkdv_occ() { return dkdv_slots<D>() * (2 * 32 * D * 2 + 256) <= 80 * 1024 ? 2 : 1; }
-template <int D, bool CAUSAL, int KT, int NW, bool DS = false, int DR = D>
+template <int D, bool CAUSAL, int KT, int NW, bool DS = false, int DR = D, bool VL = false>
 __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_kernel(AttnParams p) {
   using I = Img<D>;
   constexpr int KS = dr_ksteps<D, DR>(), DT = DR / 16;
   constexpr int QB = 32, NS = dkdv_slots<D>();
   static_assert(!DS || (KT == 2 && QB == 32), "dS tiles: 32 keys per wave, 32-query blocks");
+  static_assert(!(DS && VL), "dS tiles are indexed by the dense geometry");
   // register-ring depths of the S/dP phase (row fragments) and the dV/dK phase (transposed)
   constexpr int PA = MMPT_ATTN_BPA, PB = MMPT_ATTN_BPB;
   constexpr int KW = 16 * KT;            // keys per wave
@@ -754,6 +831,14 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
   attn_block(bx, bh);
   const int b = bh / p.Hkv, j = bh % p.Hkv;
   const int k0 = bx * KB;
+  // VL: the grid is enumerated over max_seq (p.S); S is this sequence's length, rb its first
+  // row.  A key block past the sequence's end has nothing to load or store (workgroup-uniform
+  // exit, before any barrier).
+  const int S = seq_len<VL>(p, b), rb = seq_row0<VL>(p, b);
+  if (VL && k0 >= S) return;
+  const bf16_t* qkv_b = VL ? p.qkv + (long)rb * p.ld : p.qkv;        // (VL: batch index 0 below)
+  const bf16_t* dout_b = VL ? p.dout + (long)rb * p.ld_out : p.dout;
+  const int bi = VL ? 0 : b;
   const int kw0 = k0 + wave * KW;  // this wave's first key
   const long kcol = p.koff + (long)j * p.khs, vcol = p.voff + (long)j * p.khs;
 
@@ -762,7 +847,7 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
 #pragma unroll
   for (int kt = 0; kt < KT; ++kt) {
     mykey[kt] = kw0 + kt * 16 + (lane & 15);
-    const long krow_t = (long)(b * p.S + min(mykey[kt], p.S - 1)) * p.ld;
+    const long krow_t = (long)(rb + min(mykey[kt], S - 1)) * p.ld;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       if (MMPT_ATTN_BDIAG == 10) {  // no K/V fragment loads
@@ -780,7 +865,7 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
     for (int i = 0; i < DT; ++i) dk[kt][i] = dv[kt][i] = v4f{0.f, 0.f, 0.f, 0.f};
   const float sl2 = p.scale * LOG2E;
 
-  const int nqb = (p.S + QB - 1) / QB;
+  const int nqb = (S + QB - 1) / QB;
   const int qb0 = CAUSAL ? k0 / QB : 0;
   const int cnt = nqb - qb0;   // query blocks visited per query head
   const int total = p.G * cnt; // ring sequence n = gi * cnt + (nqb - 1 - qb)
@@ -792,13 +877,13 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
     const int gi = n / cnt, qb = nqb - 1 - n % cnt;
     const int hq = j * p.G + gi;
     char* sl = smem + (n % NS) * SLOT;
-    I::template dma_rows<NW, QB>(sl, p.qkv, p.ld, (long)hq * p.hs, p.S, b, qb * QB, wave, lane, p.dr);
-    I::template dma_rows<NW, QB>(sl + IMG, p.dout, p.ld_out, (long)hq * p.dr, p.S, b, qb * QB, wave,
+    I::template dma_rows<NW, QB>(sl, qkv_b, p.ld, (long)hq * p.hs, S, bi, qb * QB, wave, lane, p.dr);
+    I::template dma_rows<NW, QB>(sl + IMG, dout_b, p.ld_out, (long)hq * p.dr, S, bi, qb * QB, wave,
                                 lane, p.dr);
     // stats (every wave writes the same 256 B, keeping the waves' vmcnt counts equal):
     // lanes 0-31 lse[q], lanes 32-63 δ[q]
     const long bhq = (long)b * p.H + hq;
-    const int q = min(qb * QB + (lane & 31), p.S - 1);
+    const int q = min(qb * QB + (lane & 31), S - 1);  // (lse / δ rows keep the stride p.S)
     const float* src = lane < 32 ? p.lse + bhq * p.S + q : p.delta + bhq * p.S + q;
     glds4(src, sl + 2 * IMG);
   };
@@ -870,7 +955,7 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
       dtr[dt] = I::template tr_frag<QB>(dimg, dt * 16, 0, lane);
       qtr[dt] = I::template tr_frag<QB>(qimg, dt * 16, 0, lane);
     }
-    const bool masked = (q0 + QB > p.S) || (kw0 + KW > p.S) || (CAUSAL && q0 < kw0 + KW - 1);
+    const bool masked = (q0 + QB > S) || (kw0 + KW > S) || (CAUSAL && q0 < kw0 + KW - 1);
     v8s pa[KT], da[KT];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
@@ -889,7 +974,7 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
           }
           if (masked) {
             const int q = q0 + qt * 16 + 4 * g + i;
-            if (q >= p.S || mykey[kt] >= p.S || (CAUSAL && mykey[kt] > q)) pr = 0.f;
+            if (q >= S || mykey[kt] >= S || (CAUSAL && mykey[kt] > q)) pr = 0.f;
           }
           s[kt][qt][i] = pr;                                // P
           dp[kt][qt][i] = pr * (dp[kt][qt][i] - dlv[i]);   // dS (unscaled)
@@ -991,8 +1076,8 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
     const int r = rw % KW;
     const uint4 v = *(const uint4*)(st + rw * I::RB + ((c ^ (r & SWM)) << 4));
     if (MMPT_ATTN_BDIAG == 11 && (v.x != 0x7fc07fc0u || i < 2 * KW / RPI - 1)) continue;  // no stores
-    if (kw0 + r < p.S && chunk_real<D>(c, p.dr))
-      *(uint4*)(p.dqkv + (long)(b * p.S + kw0 + r) * p.ld + (rw < KW ? kcol : vcol) + c * 8) = v;
+    if (kw0 + r < S && chunk_real<D>(c, p.dr))
+      *(uint4*)(p.dqkv + (long)(rb + kw0 + r) * p.ld + (rw < KW ? kcol : vcol) + c * 8) = v;
   }
 }
 
@@ -1414,7 +1499,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv_pair_kernel(AttnParams p
 // double-buffered in LDS by LDS-DMA.  Persistent like the forward (attn_item order): the
 // next item's first K/V block is staged under the current item's last key block, dQ leaves
 // through the LDS buffer that block frees, as 16-B row segments.
-template <int D, bool CAUSAL, int QT, int NW, int DR = D>
+template <int D, bool CAUSAL, int QT, int NW, int DR = D, bool VL = false>
 __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
   using I = Img<D>;
   constexpr int KS = dr_ksteps<D, DR>(), DT = DR / 16;
@@ -1425,11 +1510,24 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
   constexpr int BQ = NW * 16 * QT;
   const int nx = (p.S + BQ - 1) / BQ;
   const int nitems = nx * p.B * p.H;
+  // varlen: as in attn_fwd_kernel — empty items (query block past the sequence's end) are
+  // skipped when the item list is walked, so nothing below sees them
+  auto item_at = [&](int& k) {
+    for (;; ++k) {
+      const int w = attn_item(nitems, k);
+      if (!VL || w < 0) return w;
+      if ((nx - 1 - w % nx) * BQ < seq_len<VL>(p, w / nx / p.H)) return w;
+    }
+  };
   int it = 0;
-  int wid = attn_item(nitems, 0);
+  int wid = item_at(it);
   if (wid < 0) return;  // (workgroup-uniform)
   const float sl2 = p.scale * LOG2E;
   const int nkb_all = (p.S + ABLK - 1) / ABLK;
+  // VL: length and first row of the current item's sequence (dense: p.S and b * p.S)
+  int vsl = 0, vr0 = 0;
+  auto LEN = [&](int v) { return VL ? v : p.S; };
+  auto ROW0 = [&](int v, int bb) { return VL ? v : bb * p.S; };
 
   int b, h, bh, q0, nkb;
   long kcol, vcol;
@@ -1446,27 +1544,29 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
     q0_ = bx * BQ;
   };
   auto load_q = [&]() {
-    nkb = CAUSAL ? min(nkb_all, (q0 + BQ - 1) / ABLK + 1) : nkb_all;
+    const int nkb_s = VL ? (vsl + ABLK - 1) / ABLK : nkb_all;
+    nkb = CAUSAL ? min(nkb_s, (q0 + BQ - 1) / ABLK + 1) : nkb_s;
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
       myq[qt] = q0 + wave * 16 * QT + qt * 16 + (lane & 15);
-      const long tq = (long)(b * p.S + min(myq[qt], p.S - 1));
+      const long tq = (long)(ROW0(vr0, b) + min(myq[qt], LEN(vsl) - 1));
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         qf[qt][ks] = gfrag_m<D>(p.qkv + tq * p.ld + h * p.hs, ks, lane, p.dr);
         df[qt][ks] = gfrag_m<D>(p.dout + tq * p.ld_out + h * p.dr, ks, lane, p.dr);
       }
-      my_lse[qt] = myq[qt] < p.S ? p.lse[(long)bh * p.S + myq[qt]] * LOG2E : 0.f;
-      my_del[qt] = myq[qt] < p.S ? p.delta[(long)bh * p.S + myq[qt]] : 0.f;
+      my_lse[qt] = myq[qt] < LEN(vsl) ? p.lse[(long)bh * p.S + myq[qt]] * LOG2E : 0.f;
+      my_del[qt] = myq[qt] < LEN(vsl) ? p.delta[(long)bh * p.S + myq[qt]] : 0.f;
     }
   };
-  auto stage_kv = [&](int buf, int bb, long kc, long vc, int kb) {
+  auto stage_kv = [&](int buf, int bb, long kc, long vc, int kb, int ssl, int sr0) {
+    const int S_ = LEN(ssl);
     char* img = smem + buf * 2 * I::BYTES;
     if constexpr (D == 256) {
       // K and V pieces share their per-lane row / chunk offsets (32-bit, from a uniform base
       // at the batch's row 0): ~4 VALU per piece pair instead of ~8 of 64-bit math per piece
       constexpr int PPW = (D / 8) / NW;
-      const char* bk = (const char*)(p.qkv + (long)bb * p.S * p.ld + kc);
+      const char* bk = (const char*)(p.qkv + (VL ? (long)sr0 : (long)bb * p.S) * p.ld + kc);
       const char* bv = bk + (vc - kc) * 2;
       const int ldb = (int)p.ld * 2;
 #pragma unroll
@@ -1474,25 +1574,39 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
         const int q = wave * PPW + i;
         int r, lc;
         I::template piece<ABLK>(q, lane, r, lc);
-        const int off = min(kb * ABLK + r, p.S - 1) * ldb + (lc << 4);
+        const int off = min(kb * ABLK + r, S_ - 1) * ldb + (lc << 4);
         glds16(bk + off, img + q * 1024);
         glds16(bv + off, img + I::BYTES + q * 1024);
       }
     } else {
-      I::template dma<NW>(img, p.qkv, p.ld, kc, p.S, bb, kb * ABLK, wave, lane, p.dr);
-      I::template dma<NW>(img + I::BYTES, p.qkv, p.ld, vc, p.S, bb, kb * ABLK, wave, lane, p.dr);
+      const bf16_t* base = VL ? p.qkv + (long)sr0 * p.ld : p.qkv;  // (VL: batch index 0 below)
+      const int bi = VL ? 0 : bb;
+      I::template dma<NW>(img, base, p.ld, kc, S_, bi, kb * ABLK, wave, lane, p.dr);
+      I::template dma<NW>(img + I::BYTES, base, p.ld, vc, S_, bi, kb * ABLK, wave, lane, p.dr);
     }
   };
   decode(wid, b, h, bh, q0, kcol, vcol);
+  if constexpr (VL) {
+    vsl = seq_len<VL>(p, b);
+    vr0 = seq_row0<VL>(p, b);
+  }
   load_q();
-  stage_kv(0, b, kcol, vcol, 0);
+  stage_kv(0, b, kcol, vcol, 0, vsl, vr0);
   int par = 0;  // LDS buffer of key block kb: (kb + par) & 1
   v4f dq[QT][DT];
   for (;;) {
-  const int wid_n = attn_item(nitems, it + 1);
+  int itn = it + 1;
+  const int wid_n = item_at(itn);
   int nb = 0, nh = 0, nbh = 0, nq0 = 0;
   long nkc = 0, nvc = 0;
-  if (wid_n >= 0) decode(wid_n, nb, nh, nbh, nq0, nkc, nvc);
+  int nsl = 0, nr0 = 0;
+  if (wid_n >= 0) {
+    decode(wid_n, nb, nh, nbh, nq0, nkc, nvc);
+    if constexpr (VL) {
+      nsl = seq_len<VL>(p, nb);
+      nr0 = seq_row0<VL>(p, nb);
+    }
+  }
   vm_wait_all();
   __syncthreads();
 #pragma unroll
@@ -1503,8 +1617,8 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
     const int k0 = kb * ABLK;
     char* kimg = smem + ((kb + par) & 1) * 2 * I::BYTES;
     char* vimg = kimg + I::BYTES;
-    if (kb + 1 < nkb) stage_kv((kb + 1 + par) & 1, b, kcol, vcol, kb + 1);
-    else if (wid_n >= 0) stage_kv((kb + 1 + par) & 1, nb, nkc, nvc, 0);
+    if (kb + 1 < nkb) stage_kv((kb + 1 + par) & 1, b, kcol, vcol, kb + 1, vsl, vr0);
+    else if (wid_n >= 0) stage_kv((kb + 1 + par) & 1, nb, nkc, nvc, 0, nsl, nr0);
     v4f s[QT][4], dp[QT][4];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt)
@@ -1531,7 +1645,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
         for (int i = 0; i < 4; ++i) {
           const int key = k0 + kt * 16 + 4 * g + i;
           float pr = exp2f(s[qt][kt][i] * sl2 - my_lse[qt]);
-          if (key >= p.S || myq[qt] >= p.S || (CAUSAL && key > myq[qt])) pr = 0.f;
+          if (key >= LEN(vsl) || myq[qt] >= LEN(vsl) || (CAUSAL && key > myq[qt])) pr = 0.f;
           dp[qt][kt][i] = pr * (dp[qt][kt][i] - my_del[qt]);
         }
       dsf[qt][0] = pack_pair(dp[qt][0], dp[qt][1]);
@@ -1552,11 +1666,16 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
   }
   // past the item's last barrier: dQ through the buffer the last key block used
   const int cb = b, cq0 = q0 + wave * 16 * QT;
+  const int csl = vsl, cr0 = vr0;
   const long cqcol = (long)h * p.hs;
   char* ostage = smem + ((nkb - 1 + par) & 1) * 2 * I::BYTES + wave * (16 * QT * I::RB);
   wid = wid_n;
-  ++it;
+  it = itn;
   if (wid >= 0) {
+    if constexpr (VL) {
+      vsl = nsl;
+      vr0 = nr0;
+    }
     par = (nkb + par) & 1;
     b = nb;
     h = nh;
@@ -1586,16 +1705,16 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
     for (int i = 0; i < 16 * QT / RPI; ++i) {
       const int r = i * RPI + rr;
       const uint4 v = *(const uint4*)(ostage + r * I::RB + ((c ^ (r & SWM)) << 4));
-      if (cq0 + r < p.S && chunk_real<D>(c, p.dr))
-        *(uint4*)(p.dqkv + (long)(cb * p.S + cq0 + r) * p.ld + cqcol + c * 8) = v;
+      if (cq0 + r < LEN(csl) && chunk_real<D>(c, p.dr))
+        *(uint4*)(p.dqkv + (long)(ROW0(cr0, cb) + cq0 + r) * p.ld + cqcol + c * 8) = v;
     }
   }
 #else
   (void)ostage;
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    if (cq0 + qt * 16 + (lane & 15) >= p.S) continue;
-    bf16_t* base = p.dqkv + (long)(cb * p.S + cq0 + qt * 16 + (lane & 15)) * p.ld + cqcol;
+    if (cq0 + qt * 16 + (lane & 15) >= LEN(csl)) continue;
+    bf16_t* base = p.dqkv + (long)(ROW0(cr0, cb) + cq0 + qt * 16 + (lane & 15)) * p.ld + cqcol;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
       if (!chunk_real<D>(dt * 2, p.dr)) break;
@@ -1853,7 +1972,7 @@ int attn_slots() {
   return slots;
 }
 
-template <int D, int DR = D>
+template <int D, int DR = D, bool VL = false>
 int run_fwd(const AttnParams& p, bool causal, hipStream_t s) {
   constexpr int QT = qtiles<D>(), NW = qwaves<D>();
   const long items = (long)((p.S + NW * 16 * QT - 1) / (NW * 16 * QT)) * p.B * p.H;
@@ -1867,19 +1986,19 @@ int run_fwd(const AttnParams& p, bool causal, hipStream_t s) {
     return dim3((unsigned)(slots > 0 && items > slots ? slots : items));
   };
   if (causal)
-    attn_fwd_kernel<D, true, QT, NW, DR><<<grid_for((const void*)attn_fwd_kernel<D, true, QT, NW, DR>,
-                                                    occ[0]), NW * 64, 0, s>>>(p);
+    attn_fwd_kernel<D, true, QT, NW, DR, VL>
+        <<<grid_for((const void*)attn_fwd_kernel<D, true, QT, NW, DR, VL>, occ[0]), NW * 64, 0, s>>>(p);
   else
-    attn_fwd_kernel<D, false, QT, NW, DR><<<grid_for((const void*)attn_fwd_kernel<D, false, QT, NW, DR>,
-                                                     occ[1]), NW * 64, 0, s>>>(p);
+    attn_fwd_kernel<D, false, QT, NW, DR, VL>
+        <<<grid_for((const void*)attn_fwd_kernel<D, false, QT, NW, DR, VL>, occ[1]), NW * 64, 0, s>>>(p);
   return check_launch("attention_fwd");
 }
 
-template <int D, int DR = D>
+template <int D, int DR = D, bool VL = false>
 int run_bwd(AttnParams p, bool causal, float* delta, hipStream_t s) {
   const long rows = (long)p.B * p.S * p.H;
   constexpr int RPB = 4 * (64 / (D / 8));  // (t, h) rows per 256-thread block
-  attn_delta_kernel<D><<<(unsigned)((rows + RPB - 1) / RPB), 256, 0, s>>>(p, delta);
+  attn_delta_kernel<D, VL><<<(unsigned)((rows + RPB - 1) / RPB), 256, 0, s>>>(p, delta);
   int rc = check_launch("attention_bwd_delta");
   if (rc) return rc;
   p.delta = delta;
@@ -1897,7 +2016,9 @@ int run_bwd(AttnParams p, bool causal, float* delta, hipStream_t s) {
     const long slots = D >= 128 ? (long)attn_slots() * o : 0;
     return dim3((unsigned)(slots > 0 && items > slots ? slots : items));
   };
-  if constexpr (D == 256 && KT == 2) {
+  // (varlen runs the ring dK/dV + recomputing dQ pair at every head dim: the dS tiles and the
+  // wave-pair kernel index by the dense geometry)
+  if constexpr (D == 256 && KT == 2 && !VL) {
    if (attn_ds_mode() && p.ds != nullptr) {
     // dS tiles: the dK/dV kernel writes them, dQ = scale · dS·K reads them
     dim3 gq((p.S + 127) / 128, p.B * p.H);
@@ -1924,15 +2045,27 @@ int run_bwd(AttnParams p, bool causal, float* delta, hipStream_t s) {
    }
   }
   if (causal) {
-    attn_bwd_dkdv_ring_kernel<D, true, KT, KNW, false, DR><<<grid, KNW * 64, 0, s>>>(p);
-    attn_bwd_dq_kernel<D, true, QT, NW, DR><<<gq((const void*)attn_bwd_dq_kernel<D, true, QT, NW, DR>,
-                                                 occ[0]), NW * 64, 0, s>>>(p);
+    attn_bwd_dkdv_ring_kernel<D, true, KT, KNW, false, DR, VL><<<grid, KNW * 64, 0, s>>>(p);
+    attn_bwd_dq_kernel<D, true, QT, NW, DR, VL>
+        <<<gq((const void*)attn_bwd_dq_kernel<D, true, QT, NW, DR, VL>, occ[0]), NW * 64, 0, s>>>(p);
   } else {
-    attn_bwd_dkdv_ring_kernel<D, false, KT, KNW, false, DR><<<grid, KNW * 64, 0, s>>>(p);
-    attn_bwd_dq_kernel<D, false, QT, NW, DR><<<gq((const void*)attn_bwd_dq_kernel<D, false, QT, NW, DR>,
-                                                  occ[1]), NW * 64, 0, s>>>(p);
+    attn_bwd_dkdv_ring_kernel<D, false, KT, KNW, false, DR, VL><<<grid, KNW * 64, 0, s>>>(p);
+    attn_bwd_dq_kernel<D, false, QT, NW, DR, VL>
+        <<<gq((const void*)attn_bwd_dq_kernel<D, false, QT, NW, DR, VL>, occ[1]), NW * 64, 0, s>>>(p);
   }
   return check_launch("attention_bwd");
+}
+
+// The varlen entries' own checks, after validate(batch, max_seq, ...): the packed token count
+// takes the place of batch * seq in the 32-bit row-offset limits.
+int validate_varlen(int64_t batch, int64_t max_seq, int64_t total, const void* cu) {
+  MMPT_REQUIRE(cu != nullptr, "attention_varlen: null cu_seqlens");
+  MMPT_REQUIRE(((uintptr_t)cu & 3) == 0, "attention_varlen: cu_seqlens must be 4-B aligned");
+  MMPT_REQUIRE(total >= batch && total <= batch * max_seq,
+               "attention_varlen: total_tokens %lld outside [batch, batch * max_seq] = [%lld, %lld]",
+               (long long)total, (long long)batch, (long long)(batch * max_seq));
+  MMPT_REQUIRE(total < (1LL << 31), "attention_varlen: too many tokens");
+  return MMPT_OK;
 }
 
 int validate(int64_t batch, int64_t seq, int64_t heads, int64_t head_dim, const void* qkv,
@@ -1999,6 +2132,94 @@ extern "C" int mmpt_attention_gqa_fwd(int64_t batch, int64_t seq, int64_t heads,
     case 80: if (attn_native80()) return run_fwd<128, 80>(p, causal, s);
       return run_fwd<128>(p, causal, s);
     default: return run_fwd<128>(p, causal, s);  // 96, 112: padded to 128
+  }
+}
+
+extern "C" int mmpt_attention_varlen_fwd(int64_t batch, int64_t max_seq, int64_t total_tokens,
+                                         int64_t heads, int64_t kv_heads, int64_t head_dim,
+                                         const void* qkv, int64_t ld, int64_t head_stride,
+                                         int64_t k_offset, int64_t v_offset, int causal,
+                                         float scale, const int32_t* cu_seqlens, void* out,
+                                         int64_t ld_out, float* lse, void* stream) {
+  MMPT_REQUIRE(max_seq >= 1, "attention_varlen: max_seq %lld < 1", (long long)max_seq);
+  int rc = validate(batch, max_seq, heads, head_dim, qkv, ld, head_stride, 0);
+  if (rc) return rc;
+  rc = validate_varlen(batch, max_seq, total_tokens, cu_seqlens);
+  if (rc) return rc;
+  MMPT_REQUIRE(out && lse && ld_out % 8 == 0, "attention_varlen_fwd: bad out/lse");
+  AttnParams p{};
+  rc = set_kv(p, heads, kv_heads, k_offset, v_offset, head_stride);
+  if (rc) return rc;
+  p.qkv = (const bf16_t*)qkv;
+  p.ld = ld;
+  p.hs = head_stride;
+  p.ps = 0;
+  p.B = (int)batch;
+  p.S = (int)max_seq;
+  p.H = (int)heads;
+  p.scale = scale;
+  p.out = (bf16_t*)out;
+  p.ld_out = ld_out;
+  p.lse = lse;
+  p.dr = (int)head_dim;
+  p.cu = cu_seqlens;
+  hipStream_t s = (hipStream_t)stream;
+  switch (head_dim) {
+    case 64: return run_fwd<64, 64, true>(p, causal, s);
+    case 256: return run_fwd<256, 256, true>(p, causal, s);
+    case 80: if (attn_native80()) return run_fwd<128, 80, true>(p, causal, s);
+      return run_fwd<128, 128, true>(p, causal, s);
+    default: return run_fwd<128, 128, true>(p, causal, s);  // 96, 112: padded to 128
+  }
+}
+
+// δ only: the varlen backward takes the ring dK/dV + recomputing dQ kernels at every head dim
+extern "C" int64_t mmpt_attention_varlen_bwd_workspace_bytes(int64_t batch, int64_t max_seq,
+                                                             int64_t heads, int64_t head_dim) {
+  (void)head_dim;
+  return batch * max_seq * heads * (int64_t)sizeof(float);
+}
+
+extern "C" int mmpt_attention_varlen_bwd(int64_t batch, int64_t max_seq, int64_t total_tokens,
+                                         int64_t heads, int64_t kv_heads, int64_t head_dim,
+                                         const void* qkv, int64_t ld, int64_t head_stride,
+                                         int64_t k_offset, int64_t v_offset, int causal,
+                                         float scale, const int32_t* cu_seqlens, const void* out,
+                                         const void* dout, int64_t ld_out, const float* lse,
+                                         void* dqkv, void* workspace, void* stream) {
+  MMPT_REQUIRE(max_seq >= 1, "attention_varlen: max_seq %lld < 1", (long long)max_seq);
+  int rc = validate(batch, max_seq, heads, head_dim, qkv, ld, head_stride, 0);
+  if (rc) return rc;
+  rc = validate_varlen(batch, max_seq, total_tokens, cu_seqlens);
+  if (rc) return rc;
+  MMPT_REQUIRE(out && dout && lse && dqkv && workspace && ld_out % 8 == 0,
+               "attention_varlen_bwd: null pointer");
+  AttnParams p{};
+  rc = set_kv(p, heads, kv_heads, k_offset, v_offset, head_stride);
+  if (rc) return rc;
+  p.qkv = (const bf16_t*)qkv;
+  p.ld = ld;
+  p.hs = head_stride;
+  p.ps = 0;
+  p.B = (int)batch;
+  p.S = (int)max_seq;
+  p.H = (int)heads;
+  p.scale = scale;
+  p.ld_out = ld_out;
+  p.lse = (float*)lse;
+  p.o = (const bf16_t*)out;
+  p.dout = (const bf16_t*)dout;
+  p.dqkv = (bf16_t*)dqkv;
+  p.dr = (int)head_dim;
+  p.ds = nullptr;
+  p.cu = cu_seqlens;
+  hipStream_t s = (hipStream_t)stream;
+  switch (head_dim) {
+    case 64: return run_bwd<64, 64, true>(p, causal, (float*)workspace, s);
+    case 256: return run_bwd<256, 256, true>(p, causal, (float*)workspace, s);
+    case 80: if (attn_native80()) return run_bwd<128, 80, true>(p, causal, (float*)workspace, s);
+      return run_bwd<128, 128, true>(p, causal, (float*)workspace, s);
+    default: return run_bwd<128, 128, true>(p, causal, (float*)workspace, s);  // 96, 112: padded
   }
 }
 

@@ -65,11 +65,13 @@ __global__ __launch_bounds__(256) void colsum_stage2(int nch, int cols, const fl
 // ---------------- partial rotary embedding (in place, q and k parts) -------
 // 8 consecutive rotary dims per thread (16-B bf16 loads/stores, float4 cos/sin): the
 // same per-element arithmetic as rope_kernel; half % 8 == 0.
+// POS (mmpt_rope_inplace_pos): the table row of token t is posv[t] instead of t % seq.
+template <bool POS>
 __global__ __launch_bounds__(256) void rope8_kernel(long total, int seq, int heads, int nparts, int half,
                                                     bf16_t* qkv, long ld, long hs, long ps,
                                                     const float* __restrict__ cosb,
                                                     const float* __restrict__ sinb, int rot,
-                                                    int inverse) {
+                                                    int inverse, const int* __restrict__ posv) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int h8 = half >> 3;
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(256) void rope8_kernel(long total, int seq, int hea
   rest /= nparts;
   const int h = (int)(rest % heads);
   const long t = rest / heads;
-  const int pos = (int)(t % seq);
+  const int pos = POS ? posv[t] : (int)(t % seq);
   bf16_t* base = qkv + t * ld + h * hs + part * ps;
   const v8s a = *(const v8s*)(base + i0), bv = *(const v8s*)(base + i0 + half);
   const float* cp = cosb + (long)pos * rot + i0;
@@ -110,12 +112,12 @@ __global__ __launch_bounds__(256) void rope8_kernel(long total, int seq, int hea
 // touched rotary dims span ~2/3 of the qkv cache lines, read and partially written back.
 // Same per-element arithmetic as rope_kernel.
 // W = 2: two adjacent pairs per thread (4-B bf16x2 / float2 accesses; half even, 4-B aligned rows)
-template <int W>
+template <int W, bool POS>
 __global__ __launch_bounds__(256) void rope_pair_kernel(int total, int seq, int heads, int nparts,
                                                         int half, bf16_t* qkv, long ld, long hs,
                                                         long ps, const float* __restrict__ cosb,
                                                         const float* __restrict__ sinb, int rot,
-                                                        int inverse) {
+                                                        int inverse, const int* __restrict__ posv) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const unsigned hw = (unsigned)(half / W);
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(256) void rope_pair_kernel(int total, int seq, int 
   const int part = (int)(r1 - r2 * nparts);
   const unsigned t = r2 / (unsigned)heads;
   const int h = (int)(r2 - t * heads);
-  const int pos = (int)(t % (unsigned)seq);
+  const int pos = POS ? posv[t] : (int)(t % (unsigned)seq);
   bf16_t* base = qkv + (long)t * ld + h * hs + part * ps;
   const float* cp = cosb + pos * rot + i;
   const float* sp = sinb + pos * rot + i;
@@ -149,11 +151,12 @@ __global__ __launch_bounds__(256) void rope_pair_kernel(int total, int seq, int 
   }
 }
 
+template <bool POS>
 __global__ __launch_bounds__(256) void rope_kernel(long total, int seq, int heads, int nparts, int half,
                                                    bf16_t* qkv, long ld, long hs, long ps,
                                                    const float* __restrict__ cosb,
                                                    const float* __restrict__ sinb, int rot,
-                                                   int inverse) {
+                                                   int inverse, const int* __restrict__ posv) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int i = (int)(idx % half);
@@ -162,7 +165,7 @@ __global__ __launch_bounds__(256) void rope_kernel(long total, int seq, int head
   rest /= nparts;
   const int h = (int)(rest % heads);
   const long t = rest / heads;
-  const int pos = (int)(t % seq);
+  const int pos = POS ? posv[t] : (int)(t % seq);
   bf16_t* base = qkv + t * ld + h * hs + part * ps;
   const float x1 = bf2f(base[i]), x2 = bf2f(base[i + half]);
   const float c1 = cosb[pos * rot + i], c2 = cosb[pos * rot + i + half];
@@ -881,10 +884,12 @@ extern "C" int mmpt_colsum_f32(int64_t rows, int64_t cols, const float* part, fl
   return check_launch("colsum_f32");
 }
 
-extern "C" int mmpt_rope_inplace(int64_t tokens, int64_t seq, int64_t heads, int64_t head_dim,
-                                 int64_t rot_dims, void* qkv, int64_t ld, int64_t head_stride,
-                                 int64_t part_stride, int64_t parts, const float* cos,
-                                 const float* sin, int inverse, void* stream) {
+// mmpt_rope_inplace (posv null: position t % seq) and mmpt_rope_inplace_pos (position posv[t])
+template <bool POS>
+static int rope_launch(int64_t tokens, int64_t seq, int64_t heads, int64_t head_dim,
+                       int64_t rot_dims, void* qkv, int64_t ld, int64_t head_stride,
+                       int64_t part_stride, int64_t parts, const float* cos, const float* sin,
+                       const int* posv, int inverse, void* stream) {
   MMPT_REQUIRE(tokens > 0 && seq > 0 && heads > 0 && rot_dims > 0 && rot_dims % 2 == 0 &&
                    rot_dims <= head_dim && (parts == 1 || parts == 2),
                "rope: bad shape");
@@ -895,9 +900,9 @@ extern "C" int mmpt_rope_inplace(int64_t tokens, int64_t seq, int64_t heads, int
                    ((uintptr_t)sin & 15) == 0;
   if (vec) {
     const long total = tokens * heads * parts * (half / 8);
-    rope8_kernel<<<grid_for(total, 256, 1L << 30), 256, 0, (hipStream_t)stream>>>(
+    rope8_kernel<POS><<<grid_for(total, 256, 1L << 30), 256, 0, (hipStream_t)stream>>>(
         total, (int)seq, (int)heads, (int)parts, (int)half, (bf16_t*)qkv, ld, head_stride, part_stride, cos,
-        sin, (int)rot_dims, inverse);
+        sin, (int)rot_dims, inverse, posv);
     return check_launch("rope");
   }
   const long npairs = tokens * heads * parts * half;
@@ -908,20 +913,39 @@ extern "C" int mmpt_rope_inplace(int64_t tokens, int64_t seq, int64_t heads, int
     const long n = w2 ? npairs / 2 : npairs;
     const dim3 grid((unsigned)((n + 255) / 256));
     if (w2)
-      rope_pair_kernel<2><<<grid, 256, 0, (hipStream_t)stream>>>(
+      rope_pair_kernel<2, POS><<<grid, 256, 0, (hipStream_t)stream>>>(
           (int)n, (int)seq, (int)heads, (int)parts, (int)half, (bf16_t*)qkv, ld, head_stride,
-          part_stride, cos, sin, (int)rot_dims, inverse);
+          part_stride, cos, sin, (int)rot_dims, inverse, posv);
     else
-      rope_pair_kernel<1><<<grid, 256, 0, (hipStream_t)stream>>>(
+      rope_pair_kernel<1, POS><<<grid, 256, 0, (hipStream_t)stream>>>(
           (int)n, (int)seq, (int)heads, (int)parts, (int)half, (bf16_t*)qkv, ld, head_stride,
-          part_stride, cos, sin, (int)rot_dims, inverse);
+          part_stride, cos, sin, (int)rot_dims, inverse, posv);
     return check_launch("rope");
   }
   const long total = tokens * heads * parts * half;
-  rope_kernel<<<grid_for(total, 256, 1L << 30), 256, 0, (hipStream_t)stream>>>(
+  rope_kernel<POS><<<grid_for(total, 256, 1L << 30), 256, 0, (hipStream_t)stream>>>(
       total, (int)seq, (int)heads, (int)parts, (int)half, (bf16_t*)qkv, ld, head_stride, part_stride, cos,
-      sin, (int)rot_dims, inverse);
+      sin, (int)rot_dims, inverse, posv);
   return check_launch("rope");
+}
+
+extern "C" int mmpt_rope_inplace(int64_t tokens, int64_t seq, int64_t heads, int64_t head_dim,
+                                 int64_t rot_dims, void* qkv, int64_t ld, int64_t head_stride,
+                                 int64_t part_stride, int64_t parts, const float* cos,
+                                 const float* sin, int inverse, void* stream) {
+  return rope_launch<false>(tokens, seq, heads, head_dim, rot_dims, qkv, ld, head_stride,
+                            part_stride, parts, cos, sin, nullptr, inverse, stream);
+}
+
+extern "C" int mmpt_rope_inplace_pos(int64_t tokens, int64_t heads, int64_t head_dim,
+                                     int64_t rot_dims, void* qkv, int64_t ld, int64_t head_stride,
+                                     int64_t part_stride, int64_t parts, const float* cos,
+                                     const float* sin, int64_t table_rows, const int32_t* pos,
+                                     int inverse, void* stream) {
+  MMPT_REQUIRE(pos != nullptr && table_rows > 0, "rope_pos: null pos or empty table");
+  // (the kernels' `seq` is unused with positions; table_rows only keeps the shape check)
+  return rope_launch<true>(tokens, table_rows, heads, head_dim, rot_dims, qkv, ld, head_stride,
+                           part_stride, parts, cos, sin, pos, inverse, stream);
 }
 
 // MMPT_CE_REG=0: the two-pass cross entropy everywhere (A/B); read once, mmpt_set_switch

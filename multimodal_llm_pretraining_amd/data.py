@@ -10,6 +10,13 @@ Differences, both deliberate and documented in DESIGN.md:
   for ViT-B/16 at 224²) with label -100 on those slots — the transformers-4.47 LLaVA
   expansion the build restates; text ids then avoid the image token.
   With image_tokens=1 the reference layout (one <image> token, labels = ids) is kept.
+
+Variable-length text (`min_text_length`, default None = the fixed-length samples above,
+unchanged): the number of text tokens of sample `index` is drawn from
+U{min_text_length..full} by a generator of its own seeded from (seed, index), and the sample
+is returned at that length; `pad_collate` right-pads a list of such samples into the batch
+format of the reference's LlavaCollator (src/data/llava_data.py:169-185: input_ids,
+attention_mask with zeros and labels = -100 at the pads, pixel_values).
 """
 
 from __future__ import annotations
@@ -22,12 +29,43 @@ def _gen(seed: int, index: int) -> torch.Generator:
     return torch.Generator().manual_seed((seed * 1_000_003 + index) & 0x7FFF_FFFF_FFFF_FFFF)
 
 
+def _text_len(seed: int, index: int, lo: int | None, hi: int) -> int:
+    """Text tokens of sample `index`: hi, or U{lo..hi} from a generator of its own (the
+    sample's ids stay a prefix of the fixed-length sample's)."""
+    if lo is None:
+        return hi
+    return int(torch.randint(lo, hi + 1, (1,), generator=_gen(seed ^ 0x5EED_1E45, index)))
+
+
+def pad_collate(samples: list[dict], pad_token_id: int = 0) -> dict:
+    """Right-pad samples of unequal length to the longest: input_ids (pad_token_id at the
+    pads), attention_mask (1 / 0), labels (-100 at the pads) and, when the samples carry
+    them, stacked pixel_values."""
+    width = max(s["input_ids"].numel() for s in samples)
+    n = len(samples)
+    ids = torch.full((n, width), pad_token_id, dtype=torch.int64)
+    labels = torch.full((n, width), -100, dtype=torch.int64)
+    mask = torch.zeros((n, width), dtype=torch.int64)
+    for i, s in enumerate(samples):
+        k = s["input_ids"].numel()
+        ids[i, :k] = s["input_ids"]
+        labels[i, :k] = s["labels"]
+        mask[i, :k] = 1
+    out = {"input_ids": ids, "attention_mask": mask, "labels": labels}
+    if "pixel_values" in samples[0]:
+        out["pixel_values"] = torch.stack([s["pixel_values"] for s in samples])
+    return out
+
+
 class DummyTextModelingDataset(Dataset):
     def __init__(self, vocab_size: int, sequence_length: int, num_samples: int = 50_000,
-                 seed: int = 0) -> None:
+                 seed: int = 0, min_text_length: int | None = None) -> None:
         super().__init__()
+        if min_text_length is not None and not 1 <= min_text_length <= sequence_length:
+            raise ValueError("need 1 <= min_text_length <= sequence_length")
         self.vocab_size, self.sequence_length = vocab_size, sequence_length
         self.num_samples, self.seed = num_samples, seed
+        self.min_text_length = min_text_length
 
     def __len__(self):
         return self.num_samples
@@ -36,16 +74,21 @@ class DummyTextModelingDataset(Dataset):
         if not 0 <= index < self.num_samples:
             raise IndexError(index)
         ids = torch.randint(0, self.vocab_size, (self.sequence_length,), generator=_gen(self.seed, index))
+        ids = ids[:_text_len(self.seed, index, self.min_text_length, self.sequence_length)]
         return {"input_ids": ids, "labels": ids.clone()}
 
 
 class DummyMultimodalLanguageModelingDataset(Dataset):
     def __init__(self, vocab_size: int, sequence_length: int, image_size: int,
                  num_samples: int = 20_000, image_token_id: int = 32000, image_tokens: int = 1,
-                 seed: int = 0) -> None:
+                 seed: int = 0, min_text_length: int | None = None) -> None:
         super().__init__()
         if not 1 <= image_tokens < sequence_length:
             raise ValueError("need 1 <= image_tokens < sequence_length")
+        if min_text_length is not None and \
+                not 1 <= min_text_length <= sequence_length - image_tokens:
+            raise ValueError("need 1 <= min_text_length <= sequence_length - image_tokens")
+        self.min_text_length = min_text_length
         self.vocab_size, self.sequence_length, self.image_size = vocab_size, sequence_length, image_size
         self.num_samples, self.image_token_id, self.image_tokens = num_samples, image_token_id, image_tokens
         self.seed = seed
@@ -63,6 +106,7 @@ class DummyMultimodalLanguageModelingDataset(Dataset):
         else:  # U{0..V-1} \ {image_token_id}
             text = torch.randint(0, self.vocab_size - 1, (n_text,), generator=g)
             text = text + (text >= self.image_token_id).long()
+        text = text[:_text_len(self.seed, index, self.min_text_length, n_text)]
         ids = torch.cat([torch.full((self.image_tokens,), self.image_token_id), text])
         labels = ids.clone()
         if self.image_tokens > 1:
@@ -98,10 +142,12 @@ class PrefetchLoader:
         idx = [((self._next + i) * self.world + self.rank) % n for i in range(self.bs)]
         self._next += self.bs
         samples = [self.ds[i] for i in idx]
-        out = {}
-        for k in samples[0]:
-            t = torch.stack([s[k] for s in samples])
-            out[k] = t.pin_memory() if self.pin and torch.cuda.is_available() else t
+        if len({s["input_ids"].numel() for s in samples}) > 1:  # variable-length samples
+            out = pad_collate(samples)
+        else:
+            out = {k: torch.stack([s[k] for s in samples]) for k in samples[0]}
+        if self.pin and torch.cuda.is_available():
+            out = {k: t.pin_memory() for k, t in out.items()}
         return out
 
     def _run(self) -> None:

@@ -90,10 +90,22 @@ class Batch:
     copy is asynchronous on the current stream — building a Batch never waits for the GPU,
     so it can sit inside the timed step like the reference's `_prepare_inputs`
     (src/benchmarking/utils.py:61-63 → Trainer.training_step).  Device tensors are accepted
-    too; the counts then cost one device synchronisation."""
+    too; the counts then cost one device synchronisation.
+
+    Padded batches (`attention_mask` with zeros, right-padded as the reference's LlavaCollator
+    pads — src/data/llava_data.py:169-185): the pad positions are DROPPED here.  Labels under
+    the mask are forced to -100 and the label shift is done in the padded [B, S] layout (the
+    last real token of a row gets no label); then ids, shifted labels, the loss rows, the
+    image-token map and the embedding-backward segments are all built over the T = Σ lens
+    valid tokens, packed sequence after sequence.  `cu_seqlens` (int32 [B + 1] row offsets) and
+    `pos` (int32 [T], the position of each token inside its sequence) carry the geometry to
+    the varlen attention and the positional rope; both are None on the dense path (no mask,
+    or a mask without zeros), which is then object for object what it was without the
+    argument.  B stays the number of sequences, S the padded width."""
 
     def __init__(self, cfg: ModelConfig, input_ids: torch.Tensor, labels: torch.Tensor,
-                 pixel_values: torch.Tensor | None, device: torch.device, stream=None):
+                 pixel_values: torch.Tensor | None, device: torch.device, stream=None,
+                 attention_mask: torch.Tensor | None = None):
         """stream: stage on this (copy) stream instead of the current one — the copies and
         the segment sort then overlap the compute stream's work; `use(stream)` (called by
         Engine.forward) orders the consumer after them."""
@@ -101,24 +113,60 @@ class Batch:
         self.B, self.S = input_ids.shape
         if cfg.multimodal and pixel_values is None:
             raise ValueError("multimodal model needs pixel_values")
+        self.T, self.max_len = self.B * self.S, self.S
+        self.lens = [self.S] * self.B
+        self.cu_seqlens = self.pos = None
+        mask = self._check_mask(attention_mask)
         self._ready = None
         if stream is not None and device.type == "cuda":
             with torch.cuda.stream(stream):
-                self._stage(cfg, input_ids, labels, pixel_values, device)
+                self._stage(cfg, input_ids, labels, pixel_values, device, mask)
             self._ready = torch.cuda.Event()
             self._ready.record(stream)
         else:
-            self._stage(cfg, input_ids, labels, pixel_values, device)
+            self._stage(cfg, input_ids, labels, pixel_values, device, mask)
 
-    def _stage(self, cfg, input_ids, labels, pixel_values, device):
+    def _check_mask(self, attention_mask):
+        """None for the dense path (no mask, or no zero in it); else the host bool [B, S] mask,
+        validated as right-padded, with lens / T / max_len set from it."""
+        if attention_mask is None:
+            return None
+        if tuple(attention_mask.shape) != (self.B, self.S):
+            raise ValueError(f"attention_mask shape {tuple(attention_mask.shape)} != input_ids "
+                             f"shape {(self.B, self.S)}")
+        m = (attention_mask != 0)
+        if bool(m.all()):
+            return None
+        m = m.cpu().numpy()
+        lens = m.sum(1)
+        for b in range(self.B):
+            if lens[b] == 0:
+                raise ValueError(f"attention_mask row {b} is empty (no valid token)")
+            if not m[b, :lens[b]].all():
+                first, last = np.flatnonzero(m[b])[[0, -1]]
+                if last - first + 1 == lens[b] and last == self.S - 1:
+                    raise ValueError(f"attention_mask row {b} is left-padded; only right "
+                                     "padding is supported")
+                raise ValueError(f"attention_mask row {b} has holes; only right padding (ones "
+                                 "then zeros) is supported")
+        self.lens = [int(x) for x in lens]
+        self.T, self.max_len = int(lens.sum()), int(lens.max())
+        return torch.from_numpy(m)
+
+    def _stage(self, cfg, input_ids, labels, pixel_values, device, mask=None):
         if input_ids.device.type == "cpu" and labels.device.type == "cpu":
-            self._from_host(cfg, input_ids, labels, device)
+            self._from_host(cfg, input_ids, labels, device, mask)
         else:
-            self._from_device(cfg, input_ids, labels, device)
+            self._from_device(cfg, input_ids, labels, device, mask)
+        if mask is not None:
+            cu = np.concatenate(([0], np.cumsum(self.lens))).astype(np.int32)
+            pos = np.concatenate([np.arange(n, dtype=np.int32) for n in self.lens])
+            self.cu_seqlens = _to(torch.from_numpy(cu), device, torch.int32)
+            self.pos = _to(torch.from_numpy(pos), device, torch.int32)
         self.pixels = None
         if cfg.multimodal:
             self.pixels = _to(pixel_values, device, F32)
-        self.segments = self._segments(cfg, input_ids, device)
+        self.segments = self._segments(cfg, device)
 
     def use(self, stream) -> None:
         """Order `stream` after the staging stream and hand the staged tensors to it (the
@@ -127,20 +175,25 @@ class Batch:
             return
         stream.wait_event(self._ready)
         for t in (self.ids, self.labels, self.loss_rows, self.loss_labels, self.loss_map,
-                  self.img_map, self.pixels, *self.segments):
+                  self.img_map, self.pixels, self.cu_seqlens, self.pos, *self.segments):
             if t is not None:
                 t.record_stream(stream)
         self._ready = None
 
-    def _from_host(self, cfg, input_ids, labels, device):
+    def _from_host(self, cfg, input_ids, labels, device, mask=None):
         ids = input_ids.reshape(-1).to(torch.int64)
         lab = labels.to(torch.int64)
-        idn = ids.numpy()
-        if idn.size and (idn.min() < 0 or idn.max() >= cfg.text.vocab):
-            raise ValueError(f"token ids must lie in [0, {cfg.text.vocab})")
+        if mask is not None:  # HF's Llava loss drops the labels under the mask
+            lab = lab.masked_fill(~mask, -100)
         shifted = torch.full_like(lab, -100)
         shifted[:, :-1] = lab[:, 1:]  # ForCausalLMLoss: pad(labels, (0,1)) then [..., 1:]
         shifted = shifted.reshape(-1)
+        if mask is not None:  # drop the pads: everything below is over the T valid tokens
+            sel = mask.reshape(-1)
+            ids, shifted = ids[sel], shifted[sel]
+        idn = ids.numpy()
+        if idn.size and (idn.min() < 0 or idn.max() >= cfg.text.vocab):
+            raise ValueError(f"token ids must lie in [0, {cfg.text.vocab})")
         keep = (shifted != -100).numpy()
         _check_labels(shifted.numpy()[keep], cfg.text.n_vocab)
         self.num_items = int(keep.sum())
@@ -169,8 +222,13 @@ class Batch:
             imap = np.where(mask, np.cumsum(mask) - 1, -1).astype(np.int32)
             self.img_map = _to(torch.from_numpy(imap), device, torch.int32)
 
-    def _from_device(self, cfg, input_ids, labels, device):
+    def _from_device(self, cfg, input_ids, labels, device, mask=None):
         self.ids = input_ids.to(device, torch.int64).contiguous().view(-1)
+        sel = None
+        if mask is not None:
+            mask = mask.to(device)
+            sel = mask.reshape(-1)
+            self.ids = self.ids[sel].contiguous()
         # the embedding kernels index the table without bounds checks: validate here (the
         # path synchronises for the counts below anyway)
         if self.ids.numel():
@@ -178,9 +236,13 @@ class Batch:
             if lo_hi[0] < 0 or lo_hi[1] >= cfg.text.vocab:
                 raise ValueError(f"token ids must lie in [0, {cfg.text.vocab})")
         lab = labels.to(device, torch.int64)
+        if mask is not None:
+            lab = lab.masked_fill(~mask, -100)
         shifted = torch.full_like(lab, -100)
         shifted[:, :-1] = lab[:, 1:]
         self.labels = shifted.contiguous().view(-1)
+        if sel is not None:
+            self.labels = self.labels[sel].contiguous()
         keep = self.labels != -100
         self.num_items = int(keep.sum().item())
         if self.num_items:
@@ -204,7 +266,7 @@ class Batch:
                 raise ValueError(f"image tokens {n_img} != features {expect}")
             self.img_map = torch.where(mask, mask.cumsum(0) - 1, -1).to(torch.int32).contiguous()
 
-    def _segments(self, cfg: ModelConfig, input_ids: torch.Tensor, device) -> tuple:
+    def _segments(self, cfg: ModelConfig, device) -> tuple:
         """Index bookkeeping for the deterministic embedding backward: the
         text rows stably sorted by token id, one segment per distinct id — built on the
         device by `mmpt_embed_segments` (seg_id, seg_off, perm, nseg, bad), the count left in
@@ -212,14 +274,15 @@ class Batch:
         the numpy restatement `sort_segments`.)"""
         skip = cfg.image_token_id if cfg.multimodal else -1
         if device.type != "cuda":
-            ids = input_ids.reshape(-1).to("cpu", torch.int64).numpy()
+            ids = self.ids.to("cpu", torch.int64).numpy()
             rows = np.arange(ids.size) if skip < 0 else np.flatnonzero(ids != skip)
             return tuple(torch.from_numpy(a) for a in sort_segments(ids, rows))
         return K.embed_segments(self.ids, cfg.text.vocab, skip)
 
     @property
     def tokens(self) -> int:
-        return self.B * self.S
+        """Token rows the step computes over (the valid tokens of a padded batch)."""
+        return self.T
 
 
 def _check_labels(kept: np.ndarray, vocab_valid: int) -> None:
@@ -499,9 +562,22 @@ class Engine:
             self._fences, self._pending = [], []
 
     # -------------------------------------------------------------- text layers
+    # Padded batches (Batch.cu_seqlens set): the text layers run over the T valid tokens.  Every
+    # buffer is sized by the residual stream's row count, `S` is the longest sequence
+    # (Batch.max_len: the varlen kernels' max_seq and the lse stride), attention takes the
+    # varlen entries and the rope reads each token's position from Batch.pos.  _vl is the
+    # batch of the forward / backward in flight, or None on the dense path.
+    _vl = None
+
+    def _rope(self, qkv, S, heads, D, rot, head_stride, part_stride, inverse=False, parts=2,
+              offset=0):
+        K.rope_inplace(qkv, S, heads, D, rot, head_stride, part_stride, self.cos, self.sin,
+                       inverse=inverse, parts=parts, offset=offset,
+                       pos=None if self._vl is None else self._vl.pos)
+
     def _text_layer_fwd(self, i, x, B, S):
         t = self.cfg.text
-        T, h, H, D = B * S, t.hidden, t.heads, t.head_dim
+        T, h, H, D = x.shape[0], t.hidden, t.heads, t.head_dim
         p = f"text.layers.{i}."
         y1, y2 = self._e(T, h), self._e(T, h)
         mean, rstd = self._e(T, dtype=F32), self._e(T, dtype=F32)
@@ -509,10 +585,15 @@ class Engine:
                         rstd, self.s.p(p + "ln2.weight"), self.s.p(p + "ln2.bias"), y2)
         qkv = self._linear(y1, p + "qkv")
         if t.rot_dims > 0:
-            K.rope_inplace(qkv, S, H, D, t.rot_dims, 3 * D, D, self.cos, self.sin)
+            self._rope(qkv, S, H, D, t.rot_dims, 3 * D, D)
         a = self._e(T, h)
         lse = self._e(B * H * S, dtype=F32)
-        K.attention_fwd(qkv, B, S, H, D, 3 * D, D, True, D ** -0.5, a, lse)
+        vl = self._vl
+        if vl is None:
+            K.attention_fwd(qkv, B, S, H, D, 3 * D, D, True, D ** -0.5, a, lse)
+        else:
+            K.attention_varlen_fwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, 3 * D, D, 2 * D, True,
+                                   D ** -0.5, a, lse, max_seq=S)
         ap = self._linear(a, p + "dense")
         pre, act = self._e(T, t.ffn), self._e(T, t.ffn)
         self._linear(y2, p + "fc1", out=pre, epi=K.EPI_BF16_GELU, out2=act)
@@ -541,7 +622,7 @@ class Engine:
         (mlp + attn) sum, produced (with the fc2/dense bias gradients) by the layer
         above's fused LayerNorm backward."""
         t = self.cfg.text
-        T, h, H, D = B * S, t.hidden, t.heads, t.head_dim
+        T, h, H, D = dxn.shape[0], t.hidden, t.heads, t.head_dim
         p = f"text.layers.{i}."
         self._side_fence()
         self._unit_bwd(f"text.layers.{i}")
@@ -554,7 +635,13 @@ class Engine:
         da = self._dx(ds, p + "dense")
         self._dw(ds, a, p + "dense", bias=False)
         dqkv = self._e(T, 3 * h)
-        if t.rot_dims > 0:  # + the rope backward (in the dK / dQ epilogues at D = 256)
+        vl = self._vl
+        if vl is not None:  # varlen: ring dK/dV + recomputing dQ, then the positional rope
+            K.attention_varlen_bwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, 3 * D, D, 2 * D, True,
+                                   D ** -0.5, a, da, lse, dqkv, max_seq=S)
+            if t.rot_dims > 0:
+                self._rope(dqkv, S, H, D, t.rot_dims, 3 * D, D, inverse=True)
+        elif t.rot_dims > 0:  # + the rope backward (in the dK / dQ epilogues at D = 256)
             K.attention_bwd_rope(qkv, B, S, H, D, 3 * D, D, True, D ** -0.5, a, da, lse, dqkv,
                                  t.rot_dims, self.cos, self.sin)
         else:
@@ -577,16 +664,21 @@ class Engine:
         g|u = gate_up(RMS2 h) in one GEMM (blocked weight, SwiGLU epilogue), q/k/v in one
         GEMM, llama3 RoPE in place, GQA flash attention."""
         t = self.cfg.text
-        T, h, H, Hk, D = B * S, t.hidden, t.heads, t.n_kv, t.head_dim
+        T, h, H, Hk, D = x.shape[0], t.hidden, t.heads, t.n_kv, t.head_dim
         p = f"text.layers.{i}."
         y1, r1 = self._e(T, h), self._e(T, dtype=F32)
         K.rmsnorm_fwd(x, self.s.p(p + "ln1.weight"), t.eps, y1, r1)
         qkv = self._linear(y1, p + "qkv", bias=False)
-        K.rope_inplace(qkv, S, H, D, D, D, 0, self.cos, self.sin, parts=1)
-        K.rope_inplace(qkv, S, Hk, D, D, D, 0, self.cos, self.sin, parts=1, offset=H * D)
+        self._rope(qkv, S, H, D, D, D, 0, parts=1)
+        self._rope(qkv, S, Hk, D, D, D, 0, parts=1, offset=H * D)
         a = self._e(T, h)
         lse = self._e(B * H * S, dtype=F32)
-        K.attention_gqa_fwd(qkv, B, S, H, Hk, D, H * D, (H + Hk) * D, True, D ** -0.5, a, lse)
+        vl = self._vl
+        if vl is None:
+            K.attention_gqa_fwd(qkv, B, S, H, Hk, D, H * D, (H + Hk) * D, True, D ** -0.5, a, lse)
+        else:
+            K.attention_varlen_fwd(qkv, vl.lens, vl.cu_seqlens, H, Hk, D, D, H * D, (H + Hk) * D,
+                                   True, D ** -0.5, a, lse, max_seq=S)
         h1 = self._linear(a, p + "dense", bias=False, epi=K.EPI_F32_RESID, out2=x)
         y2, r2 = self._e(T, h), self._e(T, dtype=F32)
         K.rmsnorm_fwd(h1, self.s.p(p + "ln2.weight"), t.eps, y2, r2)
@@ -603,7 +695,7 @@ class Engine:
         """dxn: fp32 gradient of layer i's output, ds = bf16(dxn) (the down_proj output's
         gradient).  Returns (dx, bf16(dx)) for layer i-1."""
         t = self.cfg.text
-        T, h, H, Hk, D = B * S, t.hidden, t.heads, t.n_kv, t.head_dim
+        T, h, H, Hk, D = dxn.shape[0], t.hidden, t.heads, t.n_kv, t.head_dim
         p = f"text.layers.{i}."
         self._side_fence()
         self._unit_bwd(f"text.layers.{i}")
@@ -622,11 +714,15 @@ class Engine:
         da = self._dx(d1, p + "dense")
         self._dw(d1, a, p + "dense", bias=False)
         dqkv = self._e(T, t.qkv_dim)
-        K.attention_gqa_bwd(qkv, B, S, H, Hk, D, H * D, (H + Hk) * D, True, D ** -0.5, a, da, lse,
-                            dqkv)
-        K.rope_inplace(dqkv, S, H, D, D, D, 0, self.cos, self.sin, inverse=True, parts=1)
-        K.rope_inplace(dqkv, S, Hk, D, D, D, 0, self.cos, self.sin, inverse=True, parts=1,
-                       offset=H * D)
+        vl = self._vl
+        if vl is None:
+            K.attention_gqa_bwd(qkv, B, S, H, Hk, D, H * D, (H + Hk) * D, True, D ** -0.5, a, da,
+                                lse, dqkv)
+        else:
+            K.attention_varlen_bwd(qkv, vl.lens, vl.cu_seqlens, H, Hk, D, D, H * D, (H + Hk) * D,
+                                   True, D ** -0.5, a, da, lse, dqkv, max_seq=S)
+        self._rope(dqkv, S, H, D, D, D, 0, inverse=True, parts=1)
+        self._rope(dqkv, S, Hk, D, D, D, 0, inverse=True, parts=1, offset=H * D)
         dy1 = self._dx(dqkv, p + "qkv")
         self._dw(dqkv, y1, p + "qkv", bias=False)
         nxt = self._e(T, h) if i > 0 else None
@@ -771,8 +867,9 @@ class Engine:
         """Returns Σ_tokens CE (device fp32 [1]); when need_grad, dlogits are written
         (scaled by grad_scale = 1/num_items of the global batch) and the caches kept."""
         cfg, t = self.cfg, self.cfg.text
-        B, S = batch.B, batch.S
-        T = B * S
+        # S: the longest sequence — the padded width on the dense path, where T = B * S
+        B, S, T = batch.B, batch.max_len, batch.T
+        self._vl = batch if batch.cu_seqlens is not None else None
         if self.dev.type == "cuda":
             batch.use(torch.cuda.current_stream(self.dev))
         region = getattr(self.units, "region", None)
@@ -818,7 +915,8 @@ class Engine:
         """Accumulates every parameter gradient into the flat grad buffer.  `scale`
         (device scalar, e.g. autograd's grad_output) multiplies the loss gradient."""
         cfg, t = self.cfg, self.cfg.text
-        B, S = batch.B, batch.S
+        B, S, T = batch.B, batch.max_len, batch.T
+        self._vl = batch if batch.cu_seqlens is not None else None
         hL, mf, rf, yf, dlogits = self.cache.pop("head")
         if scale is not None:
             dlogits.mul_(scale.to(torch.float32))
@@ -835,9 +933,9 @@ class Engine:
             dyf = self._e(hL.shape[0], t.hidden)
             K.expand_rows(dyc, batch.loss_map, dyf)
         dh = torch.empty_like(hL)
-        self._T = B * S
+        self._T = T
         if t.llama:
-            ds = self._e(B * S, t.hidden)
+            ds = self._e(T, t.hidden)
             K.rmsnorm_bwd(hL, rf, dyf, self.s.p("text.final_ln.weight"), dh,
                           dw=self._gw("text.final_ln"), dx_bf16=ds)
             layer_bwd = self._llama_layer_bwd

@@ -240,10 +240,22 @@ def layernorm_f32_bwd(x, mean, rstd, dy, w, dx, dw, db) -> None:
 # ----------------------------------------------------------------------------- attention
 def rope_inplace(qkv: torch.Tensor, seq: int, heads: int, head_dim: int, rot_dims: int,
                  head_stride: int, part_stride: int, cos: torch.Tensor, sin: torch.Tensor,
-                 inverse: bool = False, parts: int = 2, offset: int = 0) -> None:
+                 inverse: bool = False, parts: int = 2, offset: int = 0,
+                 pos: torch.Tensor | None = None) -> None:
     """Rotate `parts` (2: q and k at part_stride apart; 1: one of them) of `heads` heads
-    starting `offset` elements into each qkv row."""
+    starting `offset` elements into each qkv row.  pos (device int32 [tokens], each in
+    [0, cos.shape[0])): the table row of every token instead of t % seq (unpadded batches;
+    `seq` is then unused)."""
     tokens = qkv.shape[0]
+    if pos is not None:
+        _check(pos, torch.int32, "rope.pos")
+        if pos.dim() != 1 or pos.numel() != tokens or not pos.is_contiguous():
+            raise ValueError(f"rope: pos must be a contiguous [tokens = {tokens}] vector")
+        _lib.call("mmpt_rope_inplace_pos", tokens, heads, head_dim, rot_dims,
+                  qkv.data_ptr() + offset * qkv.element_size(), _ld(qkv), head_stride,
+                  part_stride, parts, cos.data_ptr(), sin.data_ptr(), cos.shape[0],
+                  pos.data_ptr(), int(inverse), _stream())
+        return
     _lib.call("mmpt_rope_inplace", tokens, seq, heads, head_dim, rot_dims,
               qkv.data_ptr() + offset * qkv.element_size(), _ld(qkv), head_stride, part_stride,
               parts, cos.data_ptr(), sin.data_ptr(), int(inverse), _stream())
@@ -309,6 +321,79 @@ def attention_gqa_bwd(qkv, batch, seq, heads, kv_heads, head_dim, k_offset, v_of
     _lib.call("mmpt_attention_gqa_bwd", batch, seq, heads, kv_heads, head_dim, qkv.data_ptr(),
               _ld(qkv), head_dim, k_offset, v_offset, int(causal), float(scale), out.data_ptr(),
               dout.data_ptr(), _ld(out), lse.data_ptr(), dqkv.data_ptr(), ws.data_ptr(), _stream())
+
+
+def check_seqlens(lens, max_seq: int | None = None) -> tuple[list[int], int, int]:
+    """Validate a host-side list of sequence lengths for the varlen entries (their
+    `cu_seqlens` contents are the caller's contract).  Returns (lens, total, max_seq)."""
+    try:
+        ls = [int(x) for x in lens]
+    except (TypeError, ValueError):
+        raise ValueError("varlen: lens must be a sequence of integers") from None
+    if not ls:
+        raise ValueError("varlen: empty length list")
+    if any(x != y for x, y in zip(ls, lens)):
+        raise ValueError("varlen: lengths must be integers")
+    if min(ls) < 1:
+        raise ValueError(f"varlen: every length must be >= 1 (got {min(ls)})")
+    mx = max(ls) if max_seq is None else int(max_seq)
+    if max(ls) > mx:
+        raise ValueError(f"varlen: length {max(ls)} exceeds max_seq {mx}")
+    return ls, sum(ls), mx
+
+
+def cu_seqlens_of(lens) -> torch.Tensor:
+    """Host int32 [len(lens) + 1] row offsets of packed sequences (cu[0] = 0)."""
+    ls, _, _ = check_seqlens(lens)
+    cu = torch.zeros(len(ls) + 1, dtype=torch.int32)
+    cu[1:] = torch.tensor(ls, dtype=torch.int64).cumsum(0).to(torch.int32)
+    return cu
+
+
+def _varlen_args(qkv, lens, cu_seqlens, max_seq):
+    ls, total, mx = check_seqlens(lens, max_seq)
+    _check(cu_seqlens, torch.int32, "attention_varlen.cu_seqlens")
+    if cu_seqlens.dim() != 1 or cu_seqlens.numel() != len(ls) + 1 or \
+            not cu_seqlens.is_contiguous():
+        raise ValueError(f"varlen: cu_seqlens must be a contiguous [{len(ls) + 1}] vector")
+    if qkv.shape[0] < total:
+        raise ValueError(f"varlen: qkv has {qkv.shape[0]} rows, the lengths sum to {total}")
+    return len(ls), mx, total
+
+
+def attention_varlen_fwd(qkv, lens, cu_seqlens, heads, kv_heads, head_dim, head_stride, k_offset,
+                         v_offset, causal, scale, out, lse, max_seq: int | None = None) -> None:
+    """Attention over packed sequences: sequence b is rows [cu[b], cu[b+1]) of qkv / out.
+    lens: the host-side lengths (validated here); cu_seqlens: their device int32 prefix sums
+    (`cu_seqlens_of(lens)` on the device); lse: fp32 [len(lens) * heads * max_seq].  Layout
+    arguments as mmpt_attention_gqa_fwd (GPTNeoX / ViT: kv_heads = heads, k_offset =
+    part_stride, v_offset = 2 * part_stride)."""
+    batch, mx, total = _varlen_args(qkv, lens, cu_seqlens, max_seq)
+    if out.shape[0] < total or lse.numel() < batch * heads * mx:
+        raise ValueError("varlen: out / lse too small")
+    _lib.call("mmpt_attention_varlen_fwd", batch, mx, total, heads, kv_heads, head_dim,
+              qkv.data_ptr(), _ld(qkv), head_stride, k_offset, v_offset, int(causal),
+              float(scale), cu_seqlens.data_ptr(), out.data_ptr(), _ld(out), lse.data_ptr(),
+              _stream())
+
+
+def attention_varlen_bwd(qkv, lens, cu_seqlens, heads, kv_heads, head_dim, head_stride, k_offset,
+                         v_offset, causal, scale, out, dout, lse, dqkv,
+                         max_seq: int | None = None) -> None:
+    """Backward of attention_varlen_fwd: every q, k and v element of the first sum(lens) rows
+    of dqkv is written once."""
+    batch, mx, total = _varlen_args(qkv, lens, cu_seqlens, max_seq)
+    if min(out.shape[0], dout.shape[0], dqkv.shape[0]) < total or \
+            lse.numel() < batch * heads * mx:
+        raise ValueError("varlen: out / dout / dqkv / lse too small")
+    if _ld(dqkv) != _ld(qkv) or _ld(dout) != _ld(out):
+        raise ValueError("varlen: dqkv / dout must have the row strides of qkv / out")
+    ws = workspace(_lib.query("mmpt_attention_varlen_bwd_workspace_bytes", batch, mx, heads,
+                              head_dim), slot=3)
+    _lib.call("mmpt_attention_varlen_bwd", batch, mx, total, heads, kv_heads, head_dim,
+              qkv.data_ptr(), _ld(qkv), head_stride, k_offset, v_offset, int(causal),
+              float(scale), cu_seqlens.data_ptr(), out.data_ptr(), dout.data_ptr(), _ld(out),
+              lse.data_ptr(), dqkv.data_ptr(), ws.data_ptr(), _stream())
 
 
 # ----------------------------------------------------------------------------- loss

@@ -374,11 +374,11 @@ class MMPTForPretraining(nn.Module):
                                "(partition_out): run the step through that trainer")
         if labels is None:
             raise ValueError("the pre-training step needs labels (loss is the output)")
-        if attention_mask is not None and not bool((attention_mask != 0).all()):
-            raise NotImplementedError("padded attention masks are not on the path "
-                                      "(dummy/pre-training batches are unpadded)")
         self._refresh_if_stale()
-        batch = Batch(self.mmpt_config, input_ids, labels, pixel_values, self.store.device)
+        # a right-padded mask (the reference collators' padding=True) drops the pad tokens:
+        # the step runs over the valid tokens only (Batch); other mask shapes raise ValueError
+        batch = Batch(self.mmpt_config, input_ids, labels, pixel_values, self.store.device,
+                      attention_mask=attention_mask)
         denom = float(num_items_in_batch) if num_items_in_batch is not None \
             else float(max(1, batch.num_items))
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._plist):

@@ -241,9 +241,10 @@ class ManualTrainer:
     def stage(self, batch: dict, stream=None) -> Batch:
         """The device side of `_prepare_inputs`: host (ideally pinned) tensors are copied
         asynchronously and the index bookkeeping is built without a device sync; with
-        `stream` the staging runs on that copy stream, overlapped with the step."""
+        `stream` the staging runs on that copy stream, overlapped with the step.  A right-padded
+        `attention_mask` in the loader's dict drops the pad tokens (Batch)."""
         return Batch(self.cfg, batch["input_ids"], batch["labels"], batch.get("pixel_values"),
-                     self.device, stream=stream)
+                     self.device, stream=stream, attention_mask=batch.get("attention_mask"))
 
     def manual_training_step(self, batch: Batch, num_items_global: int,
                              last_micro_batch: bool = True) -> torch.Tensor:

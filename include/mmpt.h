@@ -115,11 +115,14 @@ int mmpt_gemm_bf16(int layout_a, int layout_b, int epilogue, int64_t M, int64_t 
  * the split-K count that mmpt_gemm_bf16 would use for this problem given `workspace_bytes`. */
 int mmpt_gemm_plan(int64_t M, int64_t N, int64_t K, int epilogue, int64_t workspace_bytes,
                    int* tile, int* splits);
-/* The exact kernel (as rocprofv3 names it, without the namespace) mmpt_gemm_bf16 launches
- * for this problem: "gemm4p_kernel<LA, LB, E>" (4-wave pipelined, 256x256 tiles) or
- * "gemm128_kernel<LA, LB, E>" (E = 100: split-K slabs), for 16-B aligned operands.  (Round 5:
- * the 8-wave gemm256 kernel is retired; gemm4p's K-tail form is "gemm4p_kt_kernel<LA, LB, E>" in
- * mmpt_gemm_last_kernel_name.)  NUL-terminated into buf. */
+/* The exact kernel (as rocprofv3 names it, without the namespace) of the main launch
+ * mmpt_gemm_bf16 makes for this problem with `workspace_bytes` of workspace and 16-B aligned
+ * operands: "gemm4p_kernel<LA, LB, E>" (4-wave pipelined, 256x256 tiles), its K-tail form
+ * "gemm4p_kt_kernel<LA, LB, E>" (K % 64 != 0), or "gemm128_kernel<LA, LB, E>" (E = 100 / 102:
+ * split-K slabs).  It is the name mmpt_gemm_last_kernel_name reports after such a call: both
+ * read the same launch schedule (before, this query never answered gemm4p_kt_kernel, and named
+ * the split launch where a weight-gradient tail split runs its main part unsplit).  (Round 5:
+ * the 8-wave gemm256 kernel is retired.)  NUL-terminated into buf. */
 int mmpt_gemm_kernel_name(int layout_a, int layout_b, int epilogue, int64_t M, int64_t N,
                           int64_t K, int64_t workspace_bytes, char* buf, int len);
 /* (ABI 11) The kernel the calling thread's most recent mmpt_gemm_bf16 call launched (its

@@ -1960,15 +1960,7 @@ constexpr int dq_qwaves() { return D == 256 ? MMPT_ATTN_DQ256 / 10 : 4; }
 // workgroups of a persistent forward launch: the CU count rounded down to whole XCDs (one
 // 128-KiB-LDS workgroup per CU); MMPT_ATTN_PERSIST=0 -> one workgroup per query block
 int attn_slots() {
-  static int slots = -1;
-  if (slots < 0) {
-    const char* e = getenv("MMPT_ATTN_PERSIST");
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 256;
-    slots = (e != nullptr && e[0] == '0') ? 0 : (cus / 8) * 8;
-  }
+  static const int slots = cu_slots("MMPT_ATTN_PERSIST");
   return slots;
 }
 

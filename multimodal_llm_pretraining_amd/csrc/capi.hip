@@ -2,6 +2,7 @@
 // SURVEY.md §8b "Errors": int status, never throw across the ABI.
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "common.h"
 
@@ -22,6 +23,16 @@ int check_launch(const char* what) {
     return (int)e;
   }
   return MMPT_OK;
+}
+
+int cu_slots(const char* off_env) {
+  const char* e = off_env != nullptr ? getenv(off_env) : nullptr;
+  if (e != nullptr && e[0] == '0') return 0;
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 256;
+  return (cus / 8) * 8;
 }
 }  // namespace mmpt
 

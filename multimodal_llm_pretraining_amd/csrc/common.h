@@ -158,6 +158,10 @@ namespace mmpt {
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 int* gemm_switch(const char* name, int* prev);  // gemm.hip: mmpt_set_switch's GEMM slots
+// capi.hip: workgroups of a persistent launch, one (or a fixed few) per CU — the device's CU count
+// rounded down to a multiple of 8 (whole XCDs), 256 when there is no device to ask; 0 when the
+// environment variable `off_env` (nullptr: none) is set to 0: one workgroup per work item
+int cu_slots(const char* off_env);
 int* misc_switch(const char* name, int* prev);  // misc.hip: MMPT_CE_REG
 }  // namespace mmpt
 

@@ -37,11 +37,10 @@
 #include <string.h>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace mmpt {
 namespace {
-
-constexpr int BK = 64;
 
 struct GemmParams {
   const bf16_t* A;
@@ -197,9 +196,6 @@ __device__ __forceinline__ void gelu_grad_pk8(const char* lut, const uint32_t* x
 // The quick-GELU epilogues (CLIP) are their own instantiations: EPI_ = 7/8/9 runs the
 // code of its base epilogue (1/2/6) with the activation chosen at compile time (a runtime
 // switch inlined both activations and spilled the 2-waves/SIMD register budget).
-// Internal epilogues: split-K fp32 slabs (EPI_SPLIT), and (round 5) the split-K form of
-// F32_ACC_COLSUM (EPI_SPLIT_CS: slabs + per-split row sums of op(A), see csa()).
-constexpr int EPI_SPLIT = 100, EPI_SPLIT_CS = 102;
 template <int E>
 constexpr int epi_base() {
   return E == MMPT_EPI_BF16_QGELU            ? MMPT_EPI_BF16_GELU
@@ -365,10 +361,8 @@ __device__ __forceinline__ void load_bf16x4(const bf16_t* p, float* o) {
   o[3] = bf2f(v.y >> 16);
 }
 
-// the big-tile kernel evaluates the erf-GELU epilogues from the LDS tables (see LUT_E0)
-#ifndef MMPT_GEMM_LUT
-#define MMPT_GEMM_LUT 1  // 0: evaluate erfc per element (A/B builds only)
-#endif
+// the big-tile kernel evaluates the erf-GELU epilogues from the LDS tables (see LUT_E0;
+// MMPT_GEMM_LUT, gemm_plan.h)
 template <int EPI_>
 constexpr bool gelu_uses_lut() {
   constexpr int E = epi_base<EPI_>();
@@ -1055,10 +1049,7 @@ __device__ __forceinline__ void epilogue4w(const GemmParams& p, v4f (&acc)[8][8]
 // K-tile; row group i + 2's pre-activations are loaded while row group i is processed, behind
 // only this epilogue's own stores (no LDS-DMA of the next tile is issued in between: the
 // compiler's vmcnt for them is exact).  Edge tiles run the same code with masked stores (the
-// launch requires 16-B aligned outputs and N % 8 == 0 for these epilogues).
-#ifndef MMPT_GEMM_4P_FAST
-#define MMPT_GEMM_4P_FAST 1
-#endif
+// launch requires 16-B aligned outputs and N % 8 == 0 for these epilogues).  MMPT_GEMM_4P_FAST (gemm_plan.h): 0 builds without it.
 // STG (round 5, measured and NOT kept: 1-2.5% slower on every plain shape and -0.3% on the
 // step, profiles/r05/stg_rejected/): the plain fast epilogue staged in the 32 KiB of LDS left
 // beside the K-tile buffers so the next tile's K-tile-1 A pieces go out before its stores and
@@ -1919,193 +1910,74 @@ __global__ __launch_bounds__(256, 1) void gemm4p_kt_kernel(GemmParams p) {
 #undef MFMA4
 #undef MFMA4Z
 
-int persistent_slots();  // (below) workgroups of a persistent launch
-
-// big-tile kernel switch, read once: MMPT_GEMM_4P=1 (default, see uses_4p), 0 = gemm128 for
-// every problem (A/B only; the 8-wave gemm256 kernel of rounds 1-3, this switch's 0 arm until
-// round 5, is retired)
-int g_gemm_4p = -1;
-int gemm_4p() {
-  if (g_gemm_4p < 0) {
-    const char* e = getenv("MMPT_GEMM_4P");
-    g_gemm_4p = e == nullptr ? 1 : atoi(e);
-  }
-  return g_gemm_4p;
-}
-// The persistent walk (round 5).  At any time an XCD's 32 CUs hold 32 consecutive work ids:
-// GROUP tile rows x 32/GROUP tile columns, whose A / B K-slices they share through the XCD's
-// L2; over the launch, A is fetched from beyond L2 once per column block and B once per row
-// block.  A (the activations, up to GBs) streams from HBM; B (a weight, <= 200 MB) mostly
-// stays in the Infinity Cache.  Measured at T = 180,992 (profiles/r05/walk/): N <= 2048
-// (8 tile columns: the dX GEMMs, the N = 2048 forwards, the weight gradients) run best with
-// GROUP = 2 (the block spans every column, A is read once) — +6..8% over round 4's GROUP = 8;
-// wider N with GROUP = 4 (+0.5..1.5%).  KREV: a workgroup's odd tiles walk K last-to-first,
-// so the A K-slices the previous tile round left in L2 are read first (qkv forward: -16%
-// L2->fabric bytes), measured +0..0.8% on the wide-N shapes and -2..4% on lm_head dX; NOT the
-// default: it changes each odd tile's fp32 summation order, hence the step's rounding (the C5
-// ZeRO-3 + offload gradient norm moved by 2.4 sigma of its bf16 noise, past its parity bar),
-// while GROUP only changes which CU computes a tile — bitwise the round-4 results.
-// Overrides (A/B): MMPT_GEMM_GROUP=<rows>, MMPT_GEMM_KREV=0/1; read once.
-int g_gemm_group = -1, g_gemm_krev = -1;  // 0 = automatic (group), 2 = automatic (krev)
-int gemm_group_env() {
-  if (g_gemm_group < 0) {
-    const char* e = getenv("MMPT_GEMM_GROUP");
-    const int v = e == nullptr ? 0 : atoi(e);
-    g_gemm_group = v >= 1 && v <= 64 ? v : 0;
-  }
-  return g_gemm_group;
-}
-int gemm_krev() {
-  if (g_gemm_krev < 0) {
-    const char* e = getenv("MMPT_GEMM_KREV");
-    g_gemm_krev = e == nullptr ? 2 : (e[0] == '1' ? 1 : 0);
-  }
-  return g_gemm_krev;
-}
-int walk_group(int tiles_n) {
-  const int g = gemm_group_env();
-  return g > 0 ? g : (tiles_n <= 8 ? 2 : 4);
-}
-int walk_krev(int tiles_n) {
-  const int k = gemm_krev();
-  (void)tiles_n;
-  return k < 2 ? k : 0;
-}
-// the forms gemm4p runs by default whatever the fast path: plain, residual, the fp32 ones and,
-// since round 5, the dQGELU (CLIP) and dSwiGLU (Llama) backward forms (general epilogue)
-constexpr bool epi_4p_default(int e) {
-  return e == MMPT_EPI_BF16 || e == MMPT_EPI_F32_RESID || e == MMPT_EPI_F32_ACC ||
-         e == MMPT_EPI_F32_STORE || e == MMPT_EPI_BF16_DQGELU ||
-         e == MMPT_EPI_BF16_DQGELU_COLSUM || e == MMPT_EPI_BF16_DSWIGLU;
-}
-// gemm4p runs a big-tile problem when the operands are both K-contiguous or both
-// row-contiguous (the weight-gradient form, split-K included) and K is a whole number of
-// K-tiles (every split too: kchunk is a multiple of 64).  epi = the launch epilogue
-// (quick-GELU forms included, EPI_SPLIT for split-K slabs).  Default (1): every epilogue with
-// the fast whole-tile path (plain, erf-GELU, erf-dGELU (+ column sums), and since round 5 the
-// quick-GELU and SwiGLU forwards from their tables) and the general-path ones above (fp32
-// residual / accumulate / store, split-K slabs, dQGELU, dSwiGLU): +5..10% over round 4's
-// 8-wave kernel at the model shapes (profiles/r04/gemm4p_ab/fast_epilogue_T180992.txt,
-// profiles/r05/act4p/).  Everything else runs gemm128.
-// The epilogues with the fast whole-tile path (epilogue4f) need 16-B aligned outputs and
-// operands (`aligned` = GemmParams::wide) and N % 8 == 0.
-constexpr bool epi_4p_fast(int e) {
-  return MMPT_GEMM_4P_FAST && (e == MMPT_EPI_BF16 || e == MMPT_EPI_F32_RESID ||
-                               (MMPT_GEMM_LUT && (e == MMPT_EPI_BF16_GELU || e == MMPT_EPI_BF16_DGELU ||
-                                                  e == MMPT_EPI_BF16_DGELU_COLSUM ||
-                                                  e == MMPT_EPI_BF16_QGELU ||
-                                                  e == MMPT_EPI_BF16_SWIGLU ||
-                                                  e == MMPT_EPI_BF16_DSWIGLU)));
-}
-// the forms with a K-tail (KT) instantiation: weight gradients (K_ROWS x K_ROWS, fp32 accumulate /
-// store / split-K slabs) and the plain forward (the CLIP patch embedding, K = 3 x 14 x 14)
-bool kt_form(int la, int epi) {
-  return la == MMPT_K_ROWS ? (epi == MMPT_EPI_F32_ACC || epi == MMPT_EPI_F32_STORE || epi == EPI_SPLIT ||
-                              epi == MMPT_EPI_F32_ACC_COLSUM || epi == EPI_SPLIT_CS)
-                           : epi == MMPT_EPI_BF16;
-}
-bool uses_4p(bool big, int la, int lb, int epi, int splits, int64_t N, int64_t K, bool aligned) {
-  const int g4 = gemm_4p();
-  (void)splits;
-  if (epi == MMPT_EPI_F32_ACC_COLSUM || epi == EPI_SPLIT_CS)  // (K-tail form since round 6)
-    return g4 != 0 && big && la == MMPT_K_ROWS && lb == MMPT_K_ROWS;
-  if (!big || la != lb || (K % BK != 0 && !kt_form(la, epi))) return false;
-  if (epi_4p_fast(epi) && !(aligned && N % 8 == 0)) return false;
-  if (epi == MMPT_EPI_BF16_SWIGLU && !epi_4p_fast(epi)) return false;  // no general-path form
-  if ((epi == MMPT_EPI_BF16_SWIGLU || epi == MMPT_EPI_BF16_DSWIGLU) && la != MMPT_ROWS_K)
-    return false;  // built for the model's K-contiguous operands only
-  return g4 != 0 && (epi_4p_default(epi) || epi_4p_fast(epi) || epi == EPI_SPLIT);
-}
-
 // The kernel the calling thread's last mmpt_gemm_bf16 launched (mmpt_gemm_last_kernel_name):
 // the choice depends on the operands' alignment, which a shape-only query cannot see.
 thread_local char g_last_kernel[64] = "";
 
-// G4: the big-tile kernel gemm4p (the caller checked uses_4p), else gemm128 (small problems, and
-// the big ones gemm4p does not take: mixed layouts, unaligned operands, K tails outside kt_form)
+// One launch of the schedule (gemm_plan.h): G4 = the big-tile kernel gemm4p, in its K-tail form
+// when the schedule says so, else gemm128.
 template <bool G4, int LA, int LB>
-int launch_epi(int epi, const GemmParams& p, dim3 grid, hipStream_t s) {
+int launch_epi(const GemmLaunch& l, const GemmParams& p, hipStream_t s) {
+  const int epi = l.epi;
   if constexpr (G4) {
     if constexpr (LA == LB) {
-      snprintf(g_last_kernel, sizeof g_last_kernel, "gemm4p_kernel<%d, %d, %d>", LA, LB, epi);
-      const int nwg = p.tiles_m * p.tiles_n * p.splits, slots = persistent_slots();
-      const dim3 grid4(slots > 0 && nwg > slots ? slots : nwg);  // persistent: one WG per CU
-      if (p.K % BK != 0) {  // K tail (kt_form)
-        snprintf(g_last_kernel, sizeof g_last_kernel, "gemm4p_kt_kernel<%d, %d, %d>", LA, LB, epi);
+      const dim3 grid4(l.workgroups);  // persistent: one WG per CU
+#define MMPT_CASE4(KERNEL, E) \
+  case E: KERNEL<LA, LB, E><<<grid4, 256, 0, s>>>(p); return check_launch("gemm4p");
+      if (l.family == G4_KT) {  // K tail (kt_form)
         if constexpr (LA == MMPT_K_ROWS) {
           switch (epi) {
-            case MMPT_EPI_F32_ACC:
-              gemm4p_kt_kernel<LA, LB, MMPT_EPI_F32_ACC><<<grid4, 256, 0, s>>>(p);
-              return check_launch("gemm4p");
-            case MMPT_EPI_F32_STORE:
-              gemm4p_kt_kernel<LA, LB, MMPT_EPI_F32_STORE><<<grid4, 256, 0, s>>>(p);
-              return check_launch("gemm4p");
-            case EPI_SPLIT:
-              gemm4p_kt_kernel<LA, LB, EPI_SPLIT><<<grid4, 256, 0, s>>>(p);
-              return check_launch("gemm4p");
+            MMPT_CASE4(gemm4p_kt_kernel, MMPT_EPI_F32_ACC)
+            MMPT_CASE4(gemm4p_kt_kernel, MMPT_EPI_F32_STORE)
+            MMPT_CASE4(gemm4p_kt_kernel, EPI_SPLIT)
             // the fused bias-gradient row sums at token counts K % 64 != 0 (round 6): the last
             // K-tile's pieces past K read zeros, which add nothing to the sums
-            case MMPT_EPI_F32_ACC_COLSUM:
-              gemm4p_kt_kernel<LA, LB, MMPT_EPI_F32_ACC_COLSUM><<<grid4, 256, 0, s>>>(p);
-              return check_launch("gemm4p");
-            case EPI_SPLIT_CS:
-              gemm4p_kt_kernel<LA, LB, EPI_SPLIT_CS><<<grid4, 256, 0, s>>>(p);
-              return check_launch("gemm4p");
+            MMPT_CASE4(gemm4p_kt_kernel, MMPT_EPI_F32_ACC_COLSUM)
+            MMPT_CASE4(gemm4p_kt_kernel, EPI_SPLIT_CS)
             default: break;
           }
-        } else if (epi == MMPT_EPI_BF16) {
-          gemm4p_kt_kernel<LA, LB, MMPT_EPI_BF16><<<grid4, 256, 0, s>>>(p);
-          return check_launch("gemm4p");
+        } else {
+          switch (epi) {
+            MMPT_CASE4(gemm4p_kt_kernel, MMPT_EPI_BF16)
+            default: break;
+          }
         }
         set_error("gemm: no K-tail form of epilogue %d", epi);
         return MMPT_ERR_ARG;
       }
       switch (epi) {
-#define MMPT_CASE4(E) \
-  case E: gemm4p_kernel<LA, LB, E><<<grid4, 256, 0, s>>>(p); return check_launch("gemm4p");
-        MMPT_CASE4(MMPT_EPI_BF16)
-        MMPT_CASE4(MMPT_EPI_BF16_GELU)
-        MMPT_CASE4(MMPT_EPI_BF16_DGELU)
-        MMPT_CASE4(MMPT_EPI_BF16_DGELU_COLSUM)
-        MMPT_CASE4(MMPT_EPI_BF16_QGELU)
-        MMPT_CASE4(MMPT_EPI_BF16_DQGELU)
-        MMPT_CASE4(MMPT_EPI_BF16_DQGELU_COLSUM)
-        MMPT_CASE4(MMPT_EPI_F32_ACC)
-        MMPT_CASE4(MMPT_EPI_F32_STORE)
-        MMPT_CASE4(MMPT_EPI_F32_RESID)
-        MMPT_CASE4(EPI_SPLIT)
-#undef MMPT_CASE4
-        case MMPT_EPI_BF16_SWIGLU:  // (the model's layout only: x · W^T, both K-contiguous)
-          if constexpr (LA == MMPT_ROWS_K) {
-            gemm4p_kernel<LA, LB, MMPT_EPI_BF16_SWIGLU><<<grid4, 256, 0, s>>>(p);
-            return check_launch("gemm4p");
-          }
-          break;
-        case MMPT_EPI_BF16_DSWIGLU:
-          if constexpr (LA == MMPT_ROWS_K) {
-            gemm4p_kernel<LA, LB, MMPT_EPI_BF16_DSWIGLU><<<grid4, 256, 0, s>>>(p);
-            return check_launch("gemm4p");
-          }
-          break;
-        case MMPT_EPI_F32_ACC_COLSUM:  // (weight gradients: both operands [tokens][features])
-          if constexpr (LA == MMPT_K_ROWS) {
-            gemm4p_kernel<LA, LB, MMPT_EPI_F32_ACC_COLSUM><<<grid4, 256, 0, s>>>(p);
-            return check_launch("gemm4p");
-          }
-          break;
-        case EPI_SPLIT_CS:
-          if constexpr (LA == MMPT_K_ROWS) {
-            gemm4p_kernel<LA, LB, EPI_SPLIT_CS><<<grid4, 256, 0, s>>>(p);
-            return check_launch("gemm4p");
-          }
-          break;
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_BF16)
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_BF16_GELU)
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_BF16_DGELU)
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_BF16_DGELU_COLSUM)
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_BF16_QGELU)
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_BF16_DQGELU)
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_BF16_DQGELU_COLSUM)
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_F32_ACC)
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_F32_STORE)
+        MMPT_CASE4(gemm4p_kernel, MMPT_EPI_F32_RESID)
+        MMPT_CASE4(gemm4p_kernel, EPI_SPLIT)
         default: break;
       }
+      if constexpr (LA == MMPT_ROWS_K) {  // (the model's layout only: x · W^T, both K-contiguous)
+        switch (epi) {
+          MMPT_CASE4(gemm4p_kernel, MMPT_EPI_BF16_SWIGLU)
+          MMPT_CASE4(gemm4p_kernel, MMPT_EPI_BF16_DSWIGLU)
+          default: break;
+        }
+      } else {  // (weight gradients: both operands [tokens][features])
+        switch (epi) {
+          MMPT_CASE4(gemm4p_kernel, MMPT_EPI_F32_ACC_COLSUM)
+          MMPT_CASE4(gemm4p_kernel, EPI_SPLIT_CS)
+          default: break;
+        }
+      }
+#undef MMPT_CASE4
     }
     set_error("gemm: no gemm4p form of epilogue %d at layouts %d / %d", epi, LA, LB);
     return MMPT_ERR_ARG;
   } else {
-    snprintf(g_last_kernel, sizeof g_last_kernel, "gemm128_kernel<%d, %d, %d>", LA, LB, epi);
+    const dim3 grid(l.workgroups, l.splits);  // one workgroup per tile and K split
     switch (epi) {
 #define MMPT_CASE(E) \
   case E: gemm128_kernel<LA, LB, E><<<grid, 256, 0, s>>>(p); break;
@@ -2137,241 +2009,11 @@ int launch_epi(int epi, const GemmParams& p, dim3 grid, hipStream_t s) {
 }
 
 template <bool G4>
-int launch_layouts(int la, int lb, int epi, const GemmParams& p, dim3 grid, hipStream_t s) {
-  if (la == MMPT_ROWS_K && lb == MMPT_ROWS_K) return launch_epi<G4, MMPT_ROWS_K, MMPT_ROWS_K>(epi, p, grid, s);
-  if (la == MMPT_ROWS_K && lb == MMPT_K_ROWS) return launch_epi<G4, MMPT_ROWS_K, MMPT_K_ROWS>(epi, p, grid, s);
-  if (la == MMPT_K_ROWS && lb == MMPT_K_ROWS) return launch_epi<G4, MMPT_K_ROWS, MMPT_K_ROWS>(epi, p, grid, s);
-  return launch_epi<G4, MMPT_K_ROWS, MMPT_ROWS_K>(epi, p, grid, s);
-}
-
-constexpr int NUM_CUS = 256;
-
-// MMPT_GEMM_TILE=128: every GEMM on the 128x128 kernel (A/B measurements only)
-bool force_tile128() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MMPT_GEMM_TILE");
-    v = e != nullptr && atoi(e) == 128;
-  }
-  return v == 1;
-}
-
-// MMPT_GEMM_SPLITS=s: weight-gradient GEMMs on 256^2 tiles in s K-splits (A/B measurements only)
-int force_splits() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MMPT_GEMM_SPLITS");
-    v = e != nullptr ? atoi(e) : 0;
-    if (v < 0 || v > 16) v = 0;
-  }
-  return v;
-}
-
-// Non-split problems run 256^2 tiles from 128 of them on (half the CUs, one wave): at 150-225
-// tiles gemm4p beats the two 128^2 waves (ViT qkv 6304x2304x768 25.5 vs 36.9 us, fc2
-// 12608x768x3072 73.7 vs 107.7 us), at 75 it loses (19.2 -> 21.5 us); per-rank 32 / 64 steps
-// +0.2% / +0.45% (profiles/r06/bigmin/).  MMPT_GEMM_BIG_MIN=t overrides (A/B measurements only).
-int64_t big_min_tiles() {
-  static int64_t v = -1;
-  if (v < 0) {
-    const char* e = getenv("MMPT_GEMM_BIG_MIN");
-    v = e != nullptr && atoi(e) > 0 ? atoi(e) : 128;
-  }
-  return v;
-}
-
-struct Plan {
-  bool big;   // 256x256 tile
-  int splits;
-  int kchunk;
-};
-
-Plan plan(int64_t M, int64_t N, int64_t K, int epi) {
-  Plan pl{};
-  const int64_t t256 = ((M + 255) / 256) * ((N + 255) / 256);
-  const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128);
-  pl.big = t256 >= big_min_tiles() || epi == MMPT_EPI_BF16_SWIGLU;  // SWIGLU pairs 128-col quadrants
-  if (force_tile128() && epi != MMPT_EPI_BF16_SWIGLU) pl.big = false;  // A/B only
-  pl.splits = 1;
-  pl.kchunk = (int)K;
-  const bool splittable = epi == MMPT_EPI_F32_ACC || epi == MMPT_EPI_F32_STORE ||
-                          epi == MMPT_EPI_F32_ACC_COLSUM;  // (the same plan as F32_ACC)
-  if (splittable) {
-    // weight gradients: K = tokens. Pick (tile, splits) minimising the padded wave
-    // count ceil(blocks / slots) / blocks-work, slots = 256 (256^2, 1 per CU) or
-    // 512 (128^2, 2 per CU); keep >= 1024 k per split and <= 16 splits (<= 2 from 512 tiles).
-    // Model: a CU fully busy with one 256^2 block retires 4 128^2-tile units in 4 time
-    // units; with two 128^2 blocks it retires 2 units in 2.67 (128^2 runs at ~0.75x the
-    // 256^2 rate).  Slab write+read adds sp*8 B per output element vs 2K flops per
-    // element: factor (1 + sp*800/K) at ~5 TB/s : ~1 PF/s.
-    double best = 1e30;
-    for (int big = 1; big >= 0; --big) {
-      const int64_t tiles = big ? t256 : t128;
-      const int64_t slots = big ? NUM_CUS : 2 * NUM_CUS;
-      const double wave_cost = big ? 4.0 : 2.67;
-      // (many tiles: up to 4 splits, which evens out the last wave — lm_head's weight
-      // gradient, 1576 tiles = 6.2 rounds of 256, runs 25 rounds of a quarter of the K:
-      // 1108 / 1141 / 1149 / 1165 TF/s at 1 / 2 / 3 / 4 splits, profiles/r04/d80/)
-      const int64_t max_sp = tiles < 2 * slots ? 16 : 4;
-      for (int64_t sp = 1; sp <= max_sp && (sp == 1 || K / sp >= 1024); ++sp) {
-        const int64_t blocks = tiles * sp;
-        const double waves = (double)((blocks + slots - 1) / slots);
-        const double cost = waves * wave_cost / (double)sp *
-                            (sp > 1 ? 1.0 + (double)sp * 800.0 / (double)K : 1.0);
-        if (cost < best - 1e-9) {
-          best = cost;
-          pl.big = big;
-          pl.splits = (int)sp;
-        }
-      }
-    }
-    if (force_splits() > 0) {
-      pl.big = true;
-      pl.splits = force_splits();
-    }
-    if (pl.splits > 1) {
-      int64_t kc = (K + pl.splits - 1) / pl.splits;
-      kc = (kc + BK - 1) / BK * BK;
-      pl.splits = (int)((K + kc - 1) / kc);
-      pl.kchunk = (int)kc;
-    }
-  }
-  return pl;
-}
-
-// Tail split (round 5).  A persistent launch runs ceil(tiles / 256) rounds; the N = 2048 GEMMs
-// of the step have 707 x 8 = 5656 tiles = 22 rounds + 24 tiles, so one CU in ten works through a
-// 23rd tile (up to ~0.2 ms at K = 8192) while the rest wait.  Instead the bottom `rows` tile rows
-// — the fewest that leave a whole number of rounds above them — run as a split-K GEMM over
-// ~all CUs (fp32 slabs in the caller's workspace) and tail_epi_kernel applies the epilogue.
-// Only for the fast plain / residual epilogues on gemm4p shapes with K >= 2048; the tail rows'
-// fp32 sums run in split order (the other rows are bitwise unchanged).  MMPT_GEMM_TAIL=0: off.
-struct TailPlan {
-  int rows = 0;    // tail tile rows (0: no tail split)
-  int splits = 0;  // K splits of the tail
-  int kchunk = 0;
-};
-int g_gemm_tail = -1;
-int gemm_tail() {
-  if (g_gemm_tail < 0) {
-    const char* e = getenv("MMPT_GEMM_TAIL");
-    g_gemm_tail = e != nullptr && e[0] == '0' ? 0 : 1;
-  }
-  return g_gemm_tail;
-}
-int g_gemm_tail128 = -1;
-bool gemm_tail128() {
-  if (g_gemm_tail128 < 0) {
-    const char* e = getenv("MMPT_GEMM_TAIL128");
-    g_gemm_tail128 = e != nullptr && e[0] == '0' ? 0 : 1;
-  }
-  return g_gemm_tail128 == 1;
-}
-int persistent_slots();
-TailPlan tail_plan(int la, int lb, int epi, int64_t M, int64_t N, int64_t K) {
-  TailPlan t;
-  if (!gemm_tail() || la != MMPT_ROWS_K || lb != MMPT_ROWS_K) return t;
-  if (epi != MMPT_EPI_BF16 && epi != MMPT_EPI_F32_RESID) return t;
-  if (K % BK != 0 || K < 2048 || N % 8 != 0) return t;
-  const Plan pl = plan(M, N, K, epi);
-  if (!pl.big || pl.splits != 1) return t;
-  const int64_t slots = persistent_slots();
-  if (slots <= 0) return t;
-  const int64_t tm = (M + 255) / 256, tn = (N + 255) / 256;
-  int64_t g = slots, b = tn;  // q = slots / gcd(tn, slots) tile rows make whole rounds
-  while (b) {
-    const int64_t r = g % b;
-    g = b;
-    b = r;
-  }
-  const int64_t q = slots / g;
-  const int64_t rt = tm % q;
-  if (rt == 0 || tm - rt < q) return t;
-  // a tail of <= 128 rows runs on 128-row tiles (gemm128, see the launch) in up to 16 splits of
-  // >= 2 K-tiles: its few rows make the slabs small (16 x 16 x 2048 fp32 = 2 MiB at C2's shape)
-  const bool small = M - (tm - rt) * 256 <= 128 && gemm_tail128();
-  const int64_t tail_tiles = small ? (N + 127) / 128 : rt * tn;
-  int64_t sp = slots / tail_tiles;
-  sp = std::min<int64_t>(sp, 16);
-  sp = std::min<int64_t>(sp, K / BK / (small ? 2 : 8));  // >= 8 (2) K-tiles per split
-  if (sp < 2) return t;
-  int64_t kc = (K / sp + BK - 1) / BK * BK;
-  t.rows = (int)rt;
-  t.splits = (int)((K + kc - 1) / kc);
-  t.kchunk = (int)kc;
-  return t;
-}
-// Weight-gradient tail split (round 6).  The planner splits a weight-gradient GEMM's K over all
-// of its tiles when they make a partial round (C5's fc1 dW: 400 tiles = 1.56 rounds, 5 splits),
-// so every tile pays the fp32 slab write + reduce — measured ~4% of the GEMM per split at K =
-// 69,568 (scripts/diag/p28_dw_splits.sh), 3x the planner's slab term.  Instead the whole rounds'
-// tile rows (or columns) run unsplit, straight into C, and only the rest is split: fc1 dW 1.91
-// -> ~1.69 full-K rounds.  F32_ACC / F32_STORE / F32_ACC_COLSUM on 256^2 tiles (the fused row
-// sums: a row tail's rows get one partial row per split there, the unsplit rows one; a column
-// tail leaves the sums to the unsplit columns, which cover all of K).  The main part's fp32
-// sums run in one pass, the tail's in split order (as before).
-// MMPT_GEMM_WTAIL=0: off; 2: tail tile columns only (tests).
-struct WTail {
-  int dim = 0;     // 0: none, 1: tail tile rows (M), 2: tail tile columns (N)
-  int lines = 0;   // whole tile rows / columns of the unsplit part
-  int splits = 0;
-  int kchunk = 0;
-};
-int g_gemm_wtail = -1;
-int gemm_wtail() {
-  if (g_gemm_wtail < 0) {
-    const char* e = getenv("MMPT_GEMM_WTAIL");
-    g_gemm_wtail = e != nullptr && e[0] == '0' ? 0 : e != nullptr && e[0] == '2' ? 2 : 1;
-  }
-  return g_gemm_wtail;
-}
-constexpr double SLAB_K = 2000.0;  // measured slab cost per split, in K units (p28 dW sweep)
-WTail wtail_plan(int epi, int64_t M, int64_t N, int64_t K) {
-  WTail w;
-  if (!gemm_wtail() || (epi != MMPT_EPI_F32_ACC && epi != MMPT_EPI_F32_STORE &&
-                        epi != MMPT_EPI_F32_ACC_COLSUM))
-    return w;
-  const Plan pl = plan(M, N, K, epi);
-  if (!pl.big || pl.splits < 2 || force_splits() > 0) return w;
-  const int64_t slots = 256, tm = (M + 255) / 256, tn = (N + 255) / 256, tiles = tm * tn;
-  const int64_t rounds = tiles / slots;
-  if (rounds < 1) return w;
-  auto split_cost = [&](int64_t t, int64_t sp) {
-    return (double)((t * sp + slots - 1) / slots) / (double)sp * (1.0 + (double)sp * SLAB_K / (double)K);
-  };
-  double best = split_cost(tiles, pl.splits) * 0.97;  // the planner's split, 3% margin
-  for (int dim = gemm_wtail() == 2 ? 2 : 1; dim <= 2; ++dim) {
-    const int64_t nl = dim == 1 ? tm : tn, other = dim == 1 ? tn : tm;
-    const int64_t lines = rounds * slots / other;
-    if (lines < 1 || lines >= nl) continue;
-    const int64_t tt = (nl - lines) * other;
-    for (int64_t sp = 2; sp <= 16 && K / sp >= 1024; ++sp) {
-      const double c = (double)((lines * other + slots - 1) / slots) + split_cost(tt, sp);
-      if (c < best - 1e-9) {
-        best = c;
-        w.dim = dim;
-        w.lines = (int)lines;
-        w.splits = (int)sp;
-      }
-    }
-  }
-  if (w.dim != 0) {
-    int64_t kc = (K + w.splits - 1) / w.splits;
-    kc = (kc + BK - 1) / BK * BK;
-    w.splits = (int)((K + kc - 1) / kc);
-    w.kchunk = (int)kc;
-  }
-  return w;
-}
-int64_t wtail_slab_bytes(int64_t M, int64_t N, const WTail& w) {
-  if (w.dim == 0) return 0;
-  const int64_t rows = w.dim == 1 ? M - (int64_t)w.lines * 256 : M;
-  const int64_t cols = w.dim == 2 ? N - (int64_t)w.lines * 256 : N;
-  return (int64_t)w.splits * rows * cols * (int64_t)sizeof(float);
-}
-
-int64_t tail_rows_of(int64_t M, const TailPlan& t) {  // matrix rows in the tail
-  return M - (((M + 255) / 256) - t.rows) * 256;
+int launch_layouts(int la, int lb, const GemmLaunch& l, const GemmParams& p, hipStream_t s) {
+  if (la == MMPT_ROWS_K && lb == MMPT_ROWS_K) return launch_epi<G4, MMPT_ROWS_K, MMPT_ROWS_K>(l, p, s);
+  if (la == MMPT_ROWS_K && lb == MMPT_K_ROWS) return launch_epi<G4, MMPT_ROWS_K, MMPT_K_ROWS>(l, p, s);
+  if (la == MMPT_K_ROWS && lb == MMPT_K_ROWS) return launch_epi<G4, MMPT_K_ROWS, MMPT_K_ROWS>(l, p, s);
+  return launch_epi<G4, MMPT_K_ROWS, MMPT_ROWS_K>(l, p, s);
 }
 
 thread_local hipEvent_t g_probe_event = nullptr;
@@ -2456,88 +2098,93 @@ int ensure_gelu_lut(hipStream_t s) {
   return MMPT_OK;
 }
 
-// workgroups of a persistent gemm4p launch: the device's CU count rounded down to a
-// multiple of 8 (whole XCDs); MMPT_GEMM_PERSIST=0 -> 0 (one workgroup per tile)
-int persistent_slots() {
-  static int slots = -1;
-  if (slots < 0) {
-    const char* e = getenv("MMPT_GEMM_PERSIST");
-    int dev = 0, cus = NUM_CUS;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = NUM_CUS;
-    slots = (e != nullptr && e[0] == '0') ? 0 : (cus / 8) * 8;
-  }
-  return slots;
+// The schedule's switches, filled once from the environment and the device (mmpt_set_switch
+// overrides some through gemm_switch below).  The A/B-only ones are not meant for production runs.
+GemmSwitches& gemm_switches() {
+  static GemmSwitches sw = [] {
+    GemmSwitches v;
+    auto env = [](const char* name, int unset) {
+      const char* e = getenv(name);
+      return e == nullptr ? unset : atoi(e);
+    };
+    auto first = [](const char* name) {  // the value's first character
+      const char* e = getenv(name);
+      return e == nullptr ? '\0' : e[0];
+    };
+    v.g4 = env("MMPT_GEMM_4P", 1);
+    v.tile128 = env("MMPT_GEMM_TILE", 0) == 128;
+    v.splits = env("MMPT_GEMM_SPLITS", 0);
+    if (v.splits < 0 || v.splits > 16) v.splits = 0;
+    v.big_min = env("MMPT_GEMM_BIG_MIN", 0) > 0 ? env("MMPT_GEMM_BIG_MIN", 0) : 128;
+    v.tail = first("MMPT_GEMM_TAIL") != '0';
+    v.tail128 = first("MMPT_GEMM_TAIL128") != '0';
+    v.wtail = first("MMPT_GEMM_WTAIL") == '0' ? 0 : first("MMPT_GEMM_WTAIL") == '2' ? 2 : 1;
+    v.group = env("MMPT_GEMM_GROUP", 0);
+    if (v.group < 1 || v.group > 64) v.group = 0;
+    const char* kr = getenv("MMPT_GEMM_KREV");
+    v.krev = kr == nullptr ? 2 : (kr[0] == '1' ? 1 : 0);
+    v.persist = first("MMPT_GEMM_PERSIST") != '0';
+    v.cus = cu_slots(nullptr);
+    return v;
+  }();
+  return sw;
 }
 
 }  // namespace
+
+// mmpt_set_switch's GEMM slots (attention.hip): the switch's storage and its current value
+int* gemm_switch(const char* name, int* prev) {
+  GemmSwitches& sw = gemm_switches();
+  int* slot = strcmp(name, "MMPT_GEMM_KREV") == 0      ? &sw.krev
+              : strcmp(name, "MMPT_GEMM_TAIL") == 0    ? &sw.tail
+              : strcmp(name, "MMPT_GEMM_WTAIL") == 0   ? &sw.wtail
+              : strcmp(name, "MMPT_GEMM_TAIL128") == 0 ? &sw.tail128
+                                                       : nullptr;
+  if (slot != nullptr) *prev = *slot;
+  return slot;
+}
 }  // namespace mmpt
 
 using namespace mmpt;
 
+// ---- the shape-only queries: the schedule of the assumed problem (gemm_plan.h)
 extern "C" int64_t mmpt_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int epilogue) {
-  const Plan pl = plan(M, N, K, epilogue);
-  if (pl.splits > 1)  // (the weight-gradient tail split needs no more than the full split)
-    return std::max((int64_t)pl.splits * M * N * (int64_t)sizeof(float),
-                    wtail_slab_bytes(M, N, wtail_plan(epilogue, M, N, K)));
-  // the tail split's slabs (ROWS_K x ROWS_K: the only layout the step's forward / dX GEMMs use)
-  const TailPlan t = tail_plan(MMPT_ROWS_K, MMPT_ROWS_K, epilogue, M, N, K);
-  return t.rows > 0 ? (int64_t)t.splits * tail_rows_of(M, t) * N * (int64_t)sizeof(float) : 0;
+  return gemm_workspace_bytes(M, N, K, epilogue, gemm_switches());
 }
-
-extern "C" int64_t mmpt_gemm_last_tail_rows(void) { return g_last_tail_rows; }
 
 extern "C" int mmpt_gemm_plan(int64_t M, int64_t N, int64_t K, int epilogue, int64_t workspace_bytes,
                               int* tile, int* splits) {
   MMPT_REQUIRE(M > 0 && N > 0 && K > 0 && tile && splits, "gemm_plan: bad arguments");
-  Plan pl = plan(M, N, K, epilogue);
-  if (pl.splits > 1 && workspace_bytes < (int64_t)pl.splits * M * N * (int64_t)sizeof(float))
-    pl.splits = 1;
-  *tile = pl.big ? 256 : 128;
-  *splits = pl.splits;
+  const GemmSchedule sch = assumed_schedule(MMPT_ROWS_K, MMPT_ROWS_K, epilogue, M, N, K,
+                                            workspace_bytes, gemm_switches());
+  *tile = sch.tile;
+  *splits = sch.splits;
   return MMPT_OK;
+}
+
+static void gemm_launch_name(char* buf, size_t len, const GemmLaunch& l, int la, int lb) {
+  snprintf(buf, len, "%s<%d, %d, %d>", gemm_family_name(l.family), la, lb, l.epi);
 }
 
 extern "C" int mmpt_gemm_kernel_name(int layout_a, int layout_b, int epilogue, int64_t M,
                                      int64_t N, int64_t K, int64_t workspace_bytes, char* buf,
                                      int len) {
   MMPT_REQUIRE(M > 0 && N > 0 && K > 0 && buf && len > 0, "gemm_kernel_name: bad arguments");
-  int tile = 0, splits = 0;
-  const int rc = mmpt_gemm_plan(M, N, K, epilogue, workspace_bytes, &tile, &splits);
-  if (rc) return rc;
-  const int epi = splits > 1 ? (epilogue == MMPT_EPI_F32_ACC_COLSUM ? EPI_SPLIT_CS : EPI_SPLIT)
-                             : epilogue;
   // (assumes 16-B aligned operands; mmpt_gemm_last_kernel_name reports the launch's own choice)
-  if (uses_4p(tile == 256, layout_a, layout_b, epi, splits, N, K, true))
-    snprintf(buf, (size_t)len, "gemm4p_kernel<%d, %d, %d>", layout_a, layout_b, epi);
-  else
-    snprintf(buf, (size_t)len, "gemm128_kernel<%d, %d, %d>", layout_a, layout_b, epi);
+  const GemmSchedule sch = assumed_schedule(layout_a, layout_b, epilogue, M, N, K, workspace_bytes,
+                                            gemm_switches());
+  gemm_launch_name(buf, (size_t)len, sch.launch[0], layout_a, layout_b);
   return MMPT_OK;
 }
 
-namespace mmpt {
-// mmpt_set_switch's GEMM slots (attention.hip): the switch's storage and its current value
-int* gemm_switch(const char* name, int* prev) {
-  if (strcmp(name, "MMPT_GEMM_KREV") == 0) {
-    *prev = gemm_krev();
-    return &g_gemm_krev;
-  }
-  if (strcmp(name, "MMPT_GEMM_TAIL") == 0) {
-    *prev = gemm_tail();
-    return &g_gemm_tail;
-  }
-  if (strcmp(name, "MMPT_GEMM_WTAIL") == 0) {
-    *prev = gemm_wtail();
-    return &g_gemm_wtail;
-  }
-  if (strcmp(name, "MMPT_GEMM_TAIL128") == 0) {
-    *prev = gemm_tail128();
-    return &g_gemm_tail128;
-  }
-  return nullptr;
+extern "C" int64_t mmpt_gemm_colsum_rows(int64_t M, int64_t N, int64_t K) {
+  return gemm_colsum_rows(M, N, K, gemm_switches());
 }
-}  // namespace mmpt
+
+extern "C" int64_t mmpt_gemm_acc_colsum_rows(int64_t M, int64_t N, int64_t K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  return gemm_acc_colsum_rows(M, N, K, gemm_switches());
+}
 
 extern "C" int mmpt_gemm_last_kernel_name(char* buf, int len) {
   MMPT_REQUIRE(buf && len > 0, "gemm_last_kernel_name: bad arguments");
@@ -2545,41 +2192,7 @@ extern "C" int mmpt_gemm_last_kernel_name(char* buf, int len) {
   return MMPT_OK;
 }
 
-namespace mmpt {
-namespace {
-// column-sum partial rows: one per 128-row half tile of the kernel that runs (gemm4p: 256-row
-// tiles; gemm128: 128-row).  The query answers for BOTH column-sum epilogues with 16-B aligned
-// operands, K-contiguous: the larger count when the erf and quick forms would take different
-// kernels (N % 8 != 0: the fast erf form needs it, the general quick form does not).
-int64_t colsum_rows_written(int64_t M, int64_t N, int64_t K, int epi, bool aligned) {
-  const Plan pl = plan(M, N, K, epi);
-  const bool g4 = pl.big && uses_4p(true, MMPT_ROWS_K, MMPT_ROWS_K, epi, 1, N, K, aligned);
-  const int64_t bm = g4 ? 256 : 128;
-  return 2 * ((M + bm - 1) / bm);
-}
-int64_t colsum_rows_query(int64_t M, int64_t N, int64_t K) {
-  return std::max(colsum_rows_written(M, N, K, MMPT_EPI_BF16_DGELU_COLSUM, true),
-                  colsum_rows_written(M, N, K, MMPT_EPI_BF16_DQGELU_COLSUM, true));
-}
-}  // namespace
-}  // namespace mmpt
-
-extern "C" int64_t mmpt_gemm_colsum_rows(int64_t M, int64_t N, int64_t K) {
-  return colsum_rows_query(M, N, K);
-}
-
-extern "C" int64_t mmpt_gemm_acc_colsum_rows(int64_t M, int64_t N, int64_t K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  const Plan pl = plan(M, N, K, MMPT_EPI_F32_ACC_COLSUM);
-  const int e = pl.splits > 1 ? EPI_SPLIT_CS : MMPT_EPI_F32_ACC_COLSUM;
-  // one partial row per (K split, 256-column tile): see gemm4p_body's CSA; the weight-gradient
-  // tail split's row tail may run more splits than the plan
-  const WTail w = pl.splits > 1 ? wtail_plan(MMPT_EPI_F32_ACC_COLSUM, M, N, K) : WTail{};
-  const int64_t sp = std::max<int64_t>(pl.splits, w.dim == 1 ? w.splits : 1);
-  return uses_4p(pl.big, MMPT_K_ROWS, MMPT_K_ROWS, e, pl.splits, N, K, true)
-             ? sp * ((N + 255) / 256)
-             : 0;
-}
+extern "C" int64_t mmpt_gemm_last_tail_rows(void) { return g_last_tail_rows; }
 
 extern "C" void mmpt_gemm_probe_event(void* hip_event) { g_probe_event = (hipEvent_t)hip_event; }
 
@@ -2641,220 +2254,116 @@ extern "C" int mmpt_gemm_bf16(int layout_a, int layout_b, int epilogue, int64_t 
                    epilogue == MMPT_EPI_BF16_SWIGLU || epilogue == MMPT_EPI_BF16_DSWIGLU,
                "gemm: bad epilogue");
 
-  Plan pl = plan(M, N, K, epilogue);
-  if (pl.splits > 1 && (workspace == nullptr ||
-                        workspace_bytes < (int64_t)pl.splits * M * N * (int64_t)sizeof(float))) {
-    pl.splits = 1;  // no workspace: single pass (same numerics, less parallelism)
-    pl.kchunk = (int)K;
-  }
-  GemmParams p;
-  p.A = (const bf16_t*)A;
-  p.B = (const bf16_t*)B;
-  p.M = (int)M;
-  p.N = (int)N;
-  p.K = (int)K;
-  p.lda = lda;
-  p.ldb = ldb;
-  p.C = C;
-  p.ldc = ldc;
-  p.bias = (const bf16_t*)bias_bf16;
-  p.aux = (const bf16_t*)aux_bf16;
-  p.ld_aux = ld_aux;
-  p.C2 = C2;
-  p.ldc2 = ldc2;
-  p.splits = pl.splits;
-  p.kchunk = pl.kchunk;
-  p.slab = (float*)workspace;
-  {
-    // 8-column epilogue needs 16-B aligned row segments in every epilogue operand
-    const int ob = (epilogue == MMPT_EPI_BF16 || epilogue == MMPT_EPI_BF16_GELU ||
-                    epilogue == MMPT_EPI_BF16_DGELU || epilogue == MMPT_EPI_BF16_DGELU_COLSUM ||
-                    epilogue == MMPT_EPI_BF16_SWIGLU || epilogue == MMPT_EPI_BF16_DSWIGLU) ? 2 : 4;
-    auto al = [](const void* q, int64_t ld, int eb) {
-      return q == nullptr || (((uintptr_t)q & 15) == 0 && (ld * eb) % 16 == 0);
-    };
-    p.wide = al(C, ldc, ob) && al(bias_bf16, 0, 2) && al(aux_bf16, ld_aux, 2) &&
-             (epilogue == MMPT_EPI_BF16_DGELU_COLSUM ? N % 4 == 0
-                                                    : al(C2, ldc2, epilogue == MMPT_EPI_F32_RESID ? 4 : 2)) &&
-             (pl.splits == 1 || (N % 8 == 0 && ((uintptr_t)workspace & 15) == 0));
-  }
+  // the problem and its schedule (gemm_plan.h)
+  // 8-column epilogue needs 16-B aligned row segments in every epilogue operand
+  const int ob = (epilogue == MMPT_EPI_BF16 || epilogue == MMPT_EPI_BF16_GELU ||
+                  epilogue == MMPT_EPI_BF16_DGELU || epilogue == MMPT_EPI_BF16_DGELU_COLSUM ||
+                  epilogue == MMPT_EPI_BF16_SWIGLU || epilogue == MMPT_EPI_BF16_DSWIGLU) ? 2 : 4;
+  auto al = [](const void* q, int64_t ld, int eb) {
+    return q == nullptr || (((uintptr_t)q & 15) == 0 && (ld * eb) % 16 == 0);
+  };
+  const bool aligned =
+      al(C, ldc, ob) && al(bias_bf16, 0, 2) && al(aux_bf16, ld_aux, 2) &&
+      (epilogue == MMPT_EPI_BF16_DGELU_COLSUM ? N % 4 == 0
+                                             : al(C2, ldc2, epilogue == MMPT_EPI_F32_RESID ? 4 : 2));
+  const GemmSwitches& sw = gemm_switches();
+  const GemmSchedule sch =
+      gemm_schedule(GemmProblem{layout_a, layout_b, launch_epilogue, M, N, K, aligned,
+                                workspace != nullptr ? workspace_bytes : 0,
+                                ((uintptr_t)workspace & 15) == 0},
+                    sw);
   hipStream_t s = (hipStream_t)stream;
-  if (epilogue == MMPT_EPI_BF16_DGELU_COLSUM) {  // (the quick form too)
-    // C2 holds mmpt_gemm_colsum_rows rows; the kernel that runs writes one per 128-row half tile
-    // (gemm4p) or per 64-row half (gemm128); rows it leaves are zeroed for the fixed-order reduce
-    const bool g4 = pl.big && uses_4p(true, layout_a, layout_b, launch_epilogue, pl.splits, N, K,
-                                      p.wide);
-    const int64_t bm = g4 ? 256 : 128, written = 2 * ((M + bm - 1) / bm);
-    const int64_t have = colsum_rows_query(M, N, K);
-    MMPT_REQUIRE(written <= have,
-                 "gemm: %lld column-sum partial rows needed, mmpt_gemm_colsum_rows gave %lld (it "
-                 "assumes 16-B aligned, K-contiguous operands)", (long long)written, (long long)have);
+
+  // C2 holds the rows the query promised (it assumes 16-B aligned operands and the full
+  // workspace); the rows this call's launches do not write in full are zeroed for the
+  // fixed-order reduce
+  if (epilogue == MMPT_EPI_BF16_DGELU_COLSUM || acc_cs) {  // (the quick form too)
+    const int64_t have = acc_cs ? gemm_acc_colsum_rows(M, N, K, sw) : gemm_colsum_rows(M, N, K, sw);
+    const int64_t written = sch.c2_rows_written, ld = acc_cs ? ldc2 : N;
+    if (acc_cs)
+      MMPT_REQUIRE(have > 0 && sch.c2_rows > 0,
+                   "gemm: F32_ACC_COLSUM does not take M=%lld N=%lld K=%lld (see "
+                   "mmpt_gemm_acc_colsum_rows)", (long long)M, (long long)N, (long long)K);
+    else
+      MMPT_REQUIRE(written <= have,
+                   "gemm: %lld column-sum partial rows needed, mmpt_gemm_colsum_rows gave %lld (it "
+                   "assumes 16-B aligned, K-contiguous operands)", (long long)written, (long long)have);
     if (written < have) {
-      const hipError_t e = hipMemsetAsync((float*)C2 + written * N, 0,
-                                          (size_t)((have - written) * N) * sizeof(float), s);
+      const hipError_t e = hipMemsetAsync((float*)C2 + written * ld, 0,
+                                          (size_t)((have - written) * ld) * sizeof(float), s);
       if (e != hipSuccess) {
-        set_error("gemm: colsum partial rows: %s", hipGetErrorString(e));
+        set_error("gemm: %scolsum partial rows: %s", acc_cs ? "acc " : "", hipGetErrorString(e));
         return (int)e;
       }
     }
   }
-  const WTail wt = pl.splits > 1 ? wtail_plan(acc_cs ? MMPT_EPI_F32_ACC_COLSUM : epilogue, M, N, K)
-                                 : WTail{};
-  if (acc_cs) {
-    // C2 holds mmpt_gemm_acc_colsum_rows rows (the planned K splits x the 256-column tiles);
-    // with less workspace this call runs fewer splits, and the rows it leaves are zeroed for the
-    // fixed-order reduce
-    const int64_t have = mmpt_gemm_acc_colsum_rows(M, N, K);
-    MMPT_REQUIRE(have > 0 && uses_4p(pl.big, layout_a, layout_b,
-                                     pl.splits > 1 ? EPI_SPLIT_CS : MMPT_EPI_F32_ACC_COLSUM,
-                                     pl.splits, N, K, true),
-                 "gemm: F32_ACC_COLSUM does not take M=%lld N=%lld K=%lld (see "
-                 "mmpt_gemm_acc_colsum_rows)", (long long)M, (long long)N, (long long)K);
-    // (under the weight-gradient tail split every row is zeroed: its parts write subsets)
-    const int64_t written = wt.dim != 0 ? 0 : pl.splits * ((N + 255) / 256);
-    if (written < have) {
-      const hipError_t e = hipMemsetAsync((float*)C2 + written * ldc2, 0,
-                                          (size_t)((have - written) * ldc2) * sizeof(float), s);
-      if (e != hipSuccess) {
-        set_error("gemm: acc colsum partial rows: %s", hipGetErrorString(e));
-        return (int)e;
-      }
-    }
-  }
-  const int epi = pl.splits > 1 ? (acc_cs ? EPI_SPLIT_CS : EPI_SPLIT) : launch_epilogue;
-  if (MMPT_GEMM_LUT && pl.big &&
-      (epi == MMPT_EPI_BF16_GELU || epi == MMPT_EPI_BF16_DGELU ||
-       epi == MMPT_EPI_BF16_DGELU_COLSUM || epi == MMPT_EPI_BF16_QGELU ||
-       epi == MMPT_EPI_BF16_DQGELU || epi == MMPT_EPI_BF16_DQGELU_COLSUM ||
-       epi == MMPT_EPI_BF16_SWIGLU || epi == MMPT_EPI_BF16_DSWIGLU)) {
+  const GemmLaunch& first = sch.launch[0];
+  if (MMPT_GEMM_LUT && sch.tile == 256 &&
+      (first.epi == MMPT_EPI_BF16_GELU || first.epi == MMPT_EPI_BF16_DGELU ||
+       first.epi == MMPT_EPI_BF16_DGELU_COLSUM || first.epi == MMPT_EPI_BF16_QGELU ||
+       first.epi == MMPT_EPI_BF16_DQGELU || first.epi == MMPT_EPI_BF16_DQGELU_COLSUM ||
+       first.epi == MMPT_EPI_BF16_SWIGLU || first.epi == MMPT_EPI_BF16_DSWIGLU)) {
     const int rc = ensure_gelu_lut(s);
     if (rc) return rc;
   }
-  // one launch over rows [.., p.M) of p (splits / kchunk / epilogue as given)
-  auto launch = [&](GemmParams& q, int e, bool small = false) -> int {
-    // gemm4p for the big problems it takes (uses_4p), gemm128 for everything else
-    const bool g4 = !small && uses_4p(pl.big, layout_a, layout_b, e, q.splits, q.N, q.K, q.wide);
-    const int bm = g4 ? 256 : 128;
-    q.tiles_m = (q.M + bm - 1) / bm;
-    q.tiles_n = (q.N + bm - 1) / bm;
-    dim3 grid(q.tiles_m * q.tiles_n, q.splits);
-    if (g4) {  // persistent: one workgroup per CU walks its XCD's run of tiles
-      const int nwg = q.tiles_m * q.tiles_n * q.splits;
-      const int slots = persistent_slots();
-      grid = dim3(slots > 0 && nwg > slots ? slots : nwg, 1);
-      q.group = walk_group(q.tiles_n);  // the walk measured for gemm4p
-      // (never with the fused row sums: their K-tile shares are split by loop index, so the
-      // columns of one tile row must walk K in the same direction)
-      const bool cs = e == MMPT_EPI_F32_ACC_COLSUM || e == EPI_SPLIT_CS;
-      q.krev = q.K % BK == 0 && !cs ? walk_krev(q.tiles_n) : 0;
-    } else {  // gemm128: one workgroup per tile, round 4's GROUP = 8, forward K order
-      q.group = gemm_group_env() > 0 ? gemm_group_env() : 8;
-      q.krev = 0;
-    }
-    return g4 ? launch_layouts<true>(layout_a, layout_b, e, q, grid, s)
-              : launch_layouts<false>(layout_a, layout_b, e, q, grid, s);
-  };
-  g_last_tail_rows = 0;
-  const TailPlan tp = pl.splits == 1 ? tail_plan(layout_a, layout_b, launch_epilogue, M, N, K)
-                                     : TailPlan{};
-  const int64_t mt = tp.rows > 0 ? tail_rows_of(M, tp) : 0;
-  if (tp.rows > 0 && p.wide && workspace != nullptr && ((uintptr_t)workspace & 15) == 0 &&
-      workspace_bytes >= (int64_t)tp.splits * mt * N * (int64_t)sizeof(float) &&
-      uses_4p(true, layout_a, layout_b, launch_epilogue, 1, N, K, true)) {
-    // rows [0, M - mt): whole rounds; rows [M - mt, M): split-K slabs + tail_epi_kernel
-    const int64_t m0 = M - mt;
-    GemmParams q = p;
-    q.M = (int)m0;
-    int rc = launch(q, launch_epilogue);
-    if (g_probe_event != nullptr) {  // bench.py: end of the main kernel (the tail is probed apart)
+
+  // the schedule's launches, each over its rectangle of C, then the finishing kernel
+  gemm_launch_name(g_last_kernel, sizeof g_last_kernel, first, layout_a, layout_b);  // (the probe's name)
+  g_last_tail_rows = sch.tail_rows;
+  GemmParams q;
+  for (int i = 0; i < sch.n; ++i) {
+    const GemmLaunch& l = sch.launch[i];
+    q.A = (const bf16_t*)A + (layout_a == MMPT_K_ROWS ? l.row0 : l.row0 * lda);
+    q.B = (const bf16_t*)B + (layout_b == MMPT_K_ROWS ? l.col0 : l.col0 * ldb);
+    q.M = (int)l.rows;
+    q.N = (int)l.cols;
+    q.K = (int)K;
+    q.lda = lda;
+    q.ldb = ldb;
+    q.C = (char*)C + (l.row0 * ldc + l.col0) * ob;
+    q.ldc = ldc;
+    q.bias = (const bf16_t*)bias_bf16;
+    q.aux = (const bf16_t*)aux_bf16;
+    q.ld_aux = ld_aux;
+    // (a split row tail's partial row sums: one row per split, at the tail's rows)
+    q.C2 = l.epi == EPI_SPLIT_CS ? (void*)((float*)C2 + l.row0) : C2;
+    q.ldc2 = ldc2;
+    q.tiles_m = l.tiles_m;
+    q.tiles_n = l.tiles_n;
+    q.splits = l.splits;
+    q.kchunk = l.kchunk;
+    q.slab = (float*)workspace;
+    q.wide = sch.wide;
+    q.group = l.group;
+    q.krev = l.krev;
+    const int rc = l.family != G128 ? launch_layouts<true>(layout_a, layout_b, l, q, s)
+                                    : launch_layouts<false>(layout_a, layout_b, l, q, s);
+    if (i == sch.probe_after && g_probe_event != nullptr) {  // bench.py: times the GEMM launches
       (void)hipEventRecord(g_probe_event, s);
       g_probe_event = nullptr;
     }
     if (rc) return rc;
-    const char* main_name = g_last_kernel;
-    char keep[64];
-    snprintf(keep, sizeof keep, "%s", main_name);
-    const int eb = launch_epilogue == MMPT_EPI_F32_RESID ? 4 : 2;
-    GemmParams t = p;
-    t.M = (int)mt;
-    t.A = p.A + m0 * lda;  // ROWS_K
-    t.C = (char*)C + m0 * ldc * eb;
-    t.splits = tp.splits;
-    t.kchunk = tp.kchunk;
-    t.slab = (float*)workspace;
-    // a tail of <= 128 rows (T = 16 * 2049 = 32,784: 16 rows) on 128-row tiles: a 256-row tile
-    // would run 16x the MFMAs its rows need (MMPT_GEMM_TAIL128=0: gemm4p, A/B only)
-    rc = launch(t, EPI_SPLIT, mt <= 128 && gemm_tail128());  // (tail_plan's `small`)
-    snprintf(g_last_kernel, sizeof g_last_kernel, "%s", keep);  // the probe names the main launch
-    if (rc) return rc;
-    const long n8 = mt * (N / 8);
-    const unsigned blocks = (unsigned)((n8 + 255) / 256);
-    const bf16_t* aux_t = aux_bf16 ? (const bf16_t*)aux_bf16 + m0 * ld_aux : nullptr;
+  }
+  if (sch.finish == FIN_NONE) return MMPT_OK;
+  const GemmLaunch& last = sch.launch[sch.n - 1];  // q: its parameters
+  if (sch.finish == FIN_TAIL_EPI) {
+    const unsigned blocks = (unsigned)((last.rows * (N / 8) + 255) / 256);
+    const bf16_t* aux_t = aux_bf16 ? (const bf16_t*)aux_bf16 + last.row0 * ld_aux : nullptr;
     if (launch_epilogue == MMPT_EPI_F32_RESID)
-      tail_epi_kernel<true><<<blocks, 256, 0, s>>>((int)mt, (int)N, tp.splits, t.slab, p.bias, aux_t,
-                                                   ld_aux, t.C, ldc, (const float*)C2 + m0 * ldc2,
+      tail_epi_kernel<true><<<blocks, 256, 0, s>>>(q.M, q.N, q.splits, q.slab, q.bias, aux_t, ld_aux,
+                                                   q.C, ldc, (const float*)C2 + last.row0 * ldc2,
                                                    ldc2);
     else
-      tail_epi_kernel<false><<<blocks, 256, 0, s>>>((int)mt, (int)N, tp.splits, t.slab, p.bias,
-                                                    nullptr, 0, t.C, ldc, nullptr, 0);
-    g_last_tail_rows = mt;
+      tail_epi_kernel<false><<<blocks, 256, 0, s>>>(q.M, q.N, q.splits, q.slab, q.bias, nullptr, 0,
+                                                    q.C, ldc, nullptr, 0);
     return check_launch("gemm_tail_epilogue");
   }
-  if (wt.dim != 0 && pl.big && p.wide && workspace != nullptr &&
-      ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= wtail_slab_bytes(M, N, wt)) {
-    // whole rounds unsplit into C, the rest split-K through slabs + splitk_reduce
-    const int64_t l0 = (int64_t)wt.lines * 256;
-    GemmParams q = p;
-    q.splits = 1;
-    q.kchunk = (int)K;
-    if (wt.dim == 1) q.M = (int)l0;
-    else q.N = (int)l0;
-    int rc = launch(q, acc_cs ? MMPT_EPI_F32_ACC_COLSUM : epilogue);
-    if (rc) return rc;
-    char keep[64];
-    snprintf(keep, sizeof keep, "%s", g_last_kernel);
-    GemmParams t = p;
-    t.splits = wt.splits;
-    t.kchunk = wt.kchunk;
-    t.slab = (float*)workspace;
-    if (wt.dim == 1) {
-      t.M = (int)(M - l0);
-      t.A = p.A + (layout_a == MMPT_K_ROWS ? l0 : l0 * lda);
-      t.C = (float*)C + l0 * ldc;
-      if (acc_cs) t.C2 = (float*)C2 + l0;  // the tail rows' partial sums, one row per split
-    } else {
-      t.N = (int)(N - l0);
-      t.B = p.B + (layout_b == MMPT_K_ROWS ? l0 : l0 * ldb);
-      t.C = (float*)C + l0;
-    }
-    rc = launch(t, acc_cs && wt.dim == 1 ? EPI_SPLIT_CS : EPI_SPLIT);
-    if (g_probe_event != nullptr) {  // bench.py: end of the GEMM launches (before the reduce)
-      (void)hipEventRecord(g_probe_event, s);
-      g_probe_event = nullptr;
-    }
-    snprintf(g_last_kernel, sizeof g_last_kernel, "%s", keep);  // the probe names the main launch
-    if (rc) return rc;
-    const long n4 = (long)t.M * (t.N / 4);
-    const unsigned blocks = (unsigned)((n4 + 255) / 256);
-    if (epilogue == MMPT_EPI_F32_ACC)
-      splitk_reduce<true><<<blocks, 256, 0, s>>>(t.M, t.N, t.splits, t.slab, (float*)t.C, ldc);
-    else
-      splitk_reduce<false><<<blocks, 256, 0, s>>>(t.M, t.N, t.splits, t.slab, (float*)t.C, ldc);
-    return check_launch("gemm_wtail_reduce");
-  }
-  int rc = launch(p, epi);
-  if (g_probe_event != nullptr) {  // bench.py: end of the main kernel (before the reduce)
-    (void)hipEventRecord(g_probe_event, s);
-    g_probe_event = nullptr;
-  }
-  if (rc || pl.splits == 1) return rc;
-  const long n4 = M * (N / 4);
-  const unsigned blocks = (unsigned)((n4 + 255) / 256);
+  const unsigned blocks = (unsigned)(((long)q.M * (q.N / 4) + 255) / 256);
   if (epilogue == MMPT_EPI_F32_ACC)
-    splitk_reduce<true><<<blocks, 256, 0, s>>>((int)M, (int)N, pl.splits, p.slab, (float*)C, ldc);
+    splitk_reduce<true><<<blocks, 256, 0, s>>>(q.M, q.N, q.splits, q.slab, (float*)q.C, ldc);
   else
-    splitk_reduce<false><<<blocks, 256, 0, s>>>((int)M, (int)N, pl.splits, p.slab, (float*)C, ldc);
-  return check_launch("gemm_splitk_reduce");
+    splitk_reduce<false><<<blocks, 256, 0, s>>>(q.M, q.N, q.splits, q.slab, (float*)q.C, ldc);
+  return check_launch(sch.n == 2 ? "gemm_wtail_reduce" : "gemm_splitk_reduce");
 }
 
 #if MMPT_GEMM_DIAG == 7

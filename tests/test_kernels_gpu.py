@@ -688,6 +688,38 @@ def test_gemm_wgrad_tail_split(K, M, N, Kd, epi, mode):
     assert bool(((got - ref).abs() <= 2 * lim).all())
 
 
+@pytest.mark.parametrize("M,N,Kd,form,kernel,tail", [
+    (512, 512, 256, "bf16", "gemm128_kernel<0, 0, 0>", 0),                # gemm128
+    (4096, 2048, 128, "bf16", "gemm4p_kernel<0, 0, 0>", 0),               # gemm4p, 128 tiles
+    # (128 tiles of 256^2 in one split: the planner prefers 512 tiles of 128^2, so no K-tail kernel)
+    (2048, 4096, 1096, "acc", "gemm128_kernel<1, 1, 3>", 0),
+    (4096, 4096, 1096, "acc", "gemm4p_kt_kernel<1, 1, 3>", 0),            # K-tail weight gradient
+    (2048, 2048, 8192, "store", "gemm4p_kernel<1, 1, 100>", 0),           # split-K weight gradient
+    (5120, 3328, 8192, "acc", "gemm4p_kernel<1, 1, 3>", 0),               # weight-gradient tail split
+    (8960, 2048, 2048, "bf16", "gemm4p_kernel<0, 0, 0>", 8960 - 8192),    # forward tail split
+    (8208, 2048, 2048, "bf16", "gemm4p_kernel<0, 0, 0>", 8208 - 8192)])   # ... with a <= 128-row tail
+def test_gemm_query_names_the_launch(K, M, N, Kd, form, kernel, tail):
+    """One small aligned problem per branch of the launch schedule (csrc/gemm_plan.h): the
+    shape-only name query, given the workspace the call gets, names the main kernel the call
+    launches (and that is the branch's kernel), the tail rows are the schedule's (the rows below
+    the last whole round of 256 tiles: 32 tile rows x 8 columns), and the result matches the fp32
+    product."""
+    from multimodal_llm_pretraining_amd import _lib
+
+    torch.manual_seed(24)
+    wgrad = form != "bf16"
+    la = lb = K.K_ROWS if wgrad else K.ROWS_K
+    epi = {"bf16": K.EPI_BF16, "acc": K.EPI_F32_ACC, "store": K.EPI_F32_STORE}[form]
+    A, B = bf(torch.randn(M, Kd, device=dev)), bf(torch.randn(N, Kd, device=dev))
+    a_st, b_st = (A.t().contiguous(), B.t().contiguous()) if wgrad else (A, B)
+    out = torch.zeros(M, N, device=dev, dtype=torch.float32 if wgrad else torch.bfloat16)
+    K.gemm(a_st, b_st, out, layout_a=la, layout_b=lb, epilogue=epi)
+    wsb = _lib.query("mmpt_gemm_workspace_bytes", M, N, Kd, epi)  # what K.gemm passed
+    assert K.gemm_last_kernel() == K.gemm_kernel_name(M, N, Kd, la, lb, epi, wsb) == kernel
+    assert _lib.query("mmpt_gemm_last_tail_rows") == tail
+    assert relerr(out, A.float() @ B.float().t()) < 5e-3
+
+
 @pytest.mark.parametrize("big", ["a", "b"])
 def test_gemm_operand_over_2gib(K, big):
     """A ROWS_K operand past 2 GiB (fc2 forward / fc1 dX read 180,992 x 8192 bf16 = 2.97 GB at the

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MMPT_ABI_VERSION 15
+#define MMPT_ABI_VERSION 16
 
 enum mmpt_status { MMPT_OK = 0, MMPT_ERR_ARG = -1, MMPT_ERR_UNSUPPORTED = -2 };
 
@@ -430,6 +430,37 @@ int mmpt_transpose_bf16(int64_t rows, int64_t cols, const void* src, int64_t ld_
 int mmpt_transpose_bf16_batched(int64_t n, const int64_t* desc, int64_t total_tiles,
                                 const void* src, void* dst, void* stream);
 
+
+/* ------------------------------------------------------------------------
+ * K16 (ABI 16)  hidden dropout: nn.Dropout at GPTNeoX's emb_dropout / post_attention_dropout /
+ * post_mlp_dropout (tf:models/gpt_neox/modeling_gpt_neox.py) and at ViTEmbeddings.dropout /
+ * ViTSelfOutput.dropout / ViTOutput.dropout (tf:models/vit/modeling_vit.py) in training mode.
+ * The masks are never stored.  Logical element e = row*h + col (64-bit, independent of any
+ * leading dimension) of dropout site `site` draws output word e % 4 of Philox4x32-10 with
+ *   key = (lo32(seed), hi32(seed)),  counter = (lo32(e/4), hi32(e/4), lo32(site), hi32(site))
+ * and is kept iff word >= floor(p * 2^32) (host arithmetic in double); kept elements are
+ * multiplied by scale = float(1 / (1 - p)), dropped ones become +0.  The same (seed, site)
+ * gives the same mask in every entry, so the backward is the forward's map on the gradient and
+ * a recomputed forward repeats it.  0 <= p < 1, h % 8 == 0, 16-B aligned pointers, leading
+ * dimensions multiples of 8 and >= h; else MMPT_ERR_ARG.
+ * ---------------------------------------------------------------------- */
+/* dst = keep ? bf16(f32(src) * scale) : +0  (one rounding: ATen's fused-dropout arithmetic).
+ * dst may alias src (same leading dimension).  Forward and backward. */
+int mmpt_dropout_bf16(int64_t rows, int64_t h, const void* src, int64_t ld_src, void* dst,
+                      int64_t ld_dst, double p, uint64_t seed, uint64_t site, void* stream);
+/* The same on dense fp32 [rows][h] (the embedding outputs, fp32 under autocast). */
+int mmpt_dropout_f32(int64_t rows, int64_t h, const float* src, float* dst, double p,
+                     uint64_t seed, uint64_t site, void* stream);
+/* The forward's residual add in one pass: out = resid + f32(v), v = drop(y; site_y) when y2 is
+ * NULL, else v = bf16(drop(y2; site_y2) + drop(y; site_y)) (GPTNeoX's parallel residual) — the
+ * rounding order of MMPT_EPI_F32_RESID.  y, y2 bf16; resid, out dense fp32 [rows][h]; out may
+ * alias resid. */
+int mmpt_dropout_add_f32(int64_t rows, int64_t h, const void* y, int64_t ld_y, uint64_t site_y,
+                         const void* y2, int64_t ld_y2, uint64_t site_y2, const float* resid,
+                         float* out, double p, uint64_t seed, void* stream);
+/* Test / diagnostic hook: keep[e] = 1 or 0 for the elements e = 0 .. n-1 of a site. */
+int mmpt_dropout_mask(int64_t n, double p, uint64_t seed, uint64_t site, uint8_t* keep,
+                      void* stream);
 
 /* ------------------------------------------------------------------------
  * ZeRO++ quantized communication (sharding = "zero_3++"): replaces DeepSpeed's

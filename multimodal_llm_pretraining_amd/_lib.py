@@ -9,11 +9,11 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_float, c_int, c_int64, c_void_p
+from ctypes import c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MMPT_LIB") or os.path.join(_HERE, "lib", "libmmpt.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _lib: ctypes.CDLL | None = None
 
@@ -21,6 +21,8 @@ P = c_void_p
 I64 = c_int64
 I32 = c_int
 F32 = c_float
+F64 = c_double
+U64 = c_uint64
 
 # name -> (restype, argtypes); mirrors include/mmpt.h one to one.
 SIGNATURES: dict[str, tuple] = {
@@ -92,6 +94,10 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_cast_f32_bf16": (I32, [I64, P, P, P]),
     "mmpt_transpose_bf16": (I32, [I64, I64, P, I64, P, I64, P]),
     "mmpt_transpose_bf16_batched": (I32, [I64, P, I64, P, P, P]),
+    "mmpt_dropout_bf16": (I32, [I64, I64, P, I64, P, I64, F64, U64, U64, P]),
+    "mmpt_dropout_f32": (I32, [I64, I64, P, P, F64, U64, U64, P]),
+    "mmpt_dropout_add_f32": (I32, [I64, I64, P, I64, U64, P, I64, U64, P, P, F64, U64, P]),
+    "mmpt_dropout_mask": (I32, [I64, F64, U64, U64, P, P]),
 }
 
 

@@ -8,7 +8,12 @@ are written out here (SURVEY.md §8c "Unavailable offline").
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
+
+
+def _check_dropout(p: float, where: str) -> None:
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{where}.hidden_dropout must lie in [0, 1), got {p!r}")
 
 
 @dataclass(frozen=True)
@@ -30,6 +35,15 @@ class VisionConfig:
     act: str = "gelu"  # "gelu" (erf) | "quick_gelu"
     pre_ln: bool = False
     patch_bias: bool = True
+    # ViTConfig.hidden_dropout_prob: ViTEmbeddings.dropout, ViTSelfOutput.dropout and
+    # ViTOutput.dropout in training mode.  The ViT tower only: CLIP has no hidden dropout
+    hidden_dropout: float = 0.0
+
+    def __post_init__(self):
+        _check_dropout(self.hidden_dropout, "VisionConfig")
+        if self.hidden_dropout > 0 and self.pre_ln:
+            raise ValueError("hidden_dropout > 0 on a CLIP tower (pre_ln): CLIPVisionConfig has "
+                             "no hidden dropout")
 
     @property
     def patch_k(self) -> int:
@@ -72,6 +86,15 @@ class TextConfig:
     rope_scaling: tuple | None = None
     tie_embeddings: bool = False
     vocab_valid: int = 0  # real vocabulary when `vocab` is padded to a multiple of 8 (0 = vocab)
+    # GPTNeoXConfig.hidden_dropout: emb_dropout, post_attention_dropout and post_mlp_dropout in
+    # training mode.  GPTNeoX only: LlamaConfig has no hidden dropout
+    hidden_dropout: float = 0.0
+
+    def __post_init__(self):
+        _check_dropout(self.hidden_dropout, "TextConfig")
+        if self.hidden_dropout > 0 and self.arch == "llama":
+            raise ValueError("hidden_dropout > 0 on a Llama text model: LlamaConfig has no "
+                             "hidden dropout")
 
     @property
     def head_dim(self) -> int:
@@ -170,6 +193,10 @@ PRESETS["tiny-mm"] = ModelConfig(
     text=TextConfig(hidden=512, layers=2, heads=2, ffn=1024, vocab=1024),
     vision=VisionConfig(hidden=128, layers=3, heads=2, ffn=256, image=64, patch=16),
     image_token_id=1023)
+# tiny-mm with hidden dropout 0.1 on both sides (with_dropout below restates it)
+PRESETS["tiny-mm-drop"] = ModelConfig(
+    text=replace(PRESETS["tiny-mm"].text, hidden_dropout=0.1),
+    vision=replace(PRESETS["tiny-mm"].vision, hidden_dropout=0.1), image_token_id=1023)
 PRESETS["tiny-lm"] = ModelConfig(text=TextConfig(hidden=256, layers=2, heads=2, ffn=512, vocab=512))
 # Pythia-2.8B's head shape (head_dim 80 -> padded D = 128 attention, 20 rotary dims)
 PRESETS["tiny-lm-d80"] = ModelConfig(text=TextConfig(hidden=320, layers=2, heads=4, ffn=640,
@@ -193,6 +220,19 @@ PRESETS["tiny-llava"] = ModelConfig(
 PRESETS["tiny-llava-frozen"] = ModelConfig(text=PRESETS["tiny-llava"].text,
                                            vision=PRESETS["tiny-llava"].vision,
                                            image_token_id=1024, freeze_tower_and_llm=True)
+
+
+def with_dropout(cfg: ModelConfig, text: float = 0.0, vision: float = 0.0) -> ModelConfig:
+    """`cfg` with the hidden-dropout probabilities set: `text` on a GPTNeoX language model,
+    `vision` on a ViT tower.  A value > 0 where HF has no hidden dropout (Llama, a CLIP tower) or
+    on a tower the model does not have raises ValueError.  Attention-probability dropout is not
+    modelled."""
+    if cfg.vision is None:
+        if vision > 0:
+            raise ValueError("vision hidden_dropout > 0 on a model without a vision tower")
+        return replace(cfg, text=replace(cfg.text, hidden_dropout=text))
+    return replace(cfg, text=replace(cfg.text, hidden_dropout=text),
+                   vision=replace(cfg.vision, hidden_dropout=vision))
 
 
 def get_config(name: str) -> ModelConfig:

@@ -1,0 +1,56 @@
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel Random Numbers: As Easy as 1, 2, 3",
+// SC'11; the Random123 constants), host and device: the counter-based generator behind the
+// hidden-dropout kernels (dropout.hip).  A stand-alone header (no HIP include) so that a plain
+// C++ program can check it against the published known answers.
+//
+// The dropout addressing (include/mmpt.h "K16"): logical element e = row*h + col of a
+// dropout site draws output word e % 4 of
+//   philox4x32_10(counter = {lo32(e/4), hi32(e/4), lo32(site), hi32(site)},
+//                 key     = {lo32(seed), hi32(seed)})
+// and is kept iff word >= floor(p * 2^32) (dropout_threshold, host arithmetic in double).
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define MMPT_PHILOX_HD __host__ __device__ inline
+#else
+#define MMPT_PHILOX_HD inline
+#endif
+
+namespace mmpt {
+
+struct philox4 {
+  uint32_t w[4];
+};
+
+constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
+constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
+
+MMPT_PHILOX_HD philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                     uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)PHILOX_M0 * c0, p1 = (uint64_t)PHILOX_M1 * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += PHILOX_W0;  // the key schedule (the bump after the last round is unused)
+    k1 += PHILOX_W1;
+  }
+  return philox4{{c0, c1, c2, c3}};
+}
+
+// The four words of elements 4*q .. 4*q + 3 of dropout site `site` under `seed`.
+MMPT_PHILOX_HD philox4 dropout_words(uint64_t q, uint64_t site, uint64_t seed) {
+  return philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)site, (uint32_t)(site >> 32),
+                       (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// Host side of the keep rule: keep iff word >= floor(p * 2^32), 0 <= p < 1 (p = 0 keeps all).
+inline uint32_t dropout_threshold(double p) { return (uint32_t)(uint64_t)(p * 4294967296.0); }
+// 1 / (1 - p) rounded once to fp32: the factor kept elements are multiplied by.
+inline float dropout_scale(double p) { return (float)(1.0 / (1.0 - p)); }
+
+}  // namespace mmpt

@@ -79,6 +79,25 @@ def sort_segments(ids: np.ndarray, rows: np.ndarray):
     return tuple(np.ascontiguousarray(a, dtype=np.int32) for a in (sid[starts], seg_off, perm))
 
 
+# Hidden-dropout site ids (mmpt_dropout_*'s 64-bit `site`): | step 32 | rank 16 | unit 12 | k 4 |
+# bits.  unit: 0 = the text embedding, 1 + i = text layer i, VISION_UNIT = the ViT embedding,
+# VISION_UNIT + 1 + i = ViT layer i (so at most 2047 layers a side); k: the site inside the
+# unit (a layer: 0 = after the attention output projection, 1 = after the MLP).
+SITE_STEPS, SITE_RANKS, SITE_UNITS, SITE_KS = 1 << 32, 1 << 16, 1 << 12, 1 << 4
+VISION_UNIT = SITE_UNITS // 2
+
+
+def dropout_site(step: int, rank: int, unit: int, k: int) -> int:
+    """The 64-bit site of a dropout mask: micro-step counter, data-parallel rank, unit, site
+    within the unit, each in its own bit field — injective over 0 <= step < 2^32, 0 <= rank <
+    2^16, 0 <= unit < 2^12, 0 <= k < 2^4; anything outside raises ValueError."""
+    for name, v, n in (("step", step, SITE_STEPS), ("rank", rank, SITE_RANKS),
+                       ("unit", unit, SITE_UNITS), ("k", k, SITE_KS)):
+        if not 0 <= v < n:
+            raise ValueError(f"dropout_site: {name} {v} outside [0, {n})")
+    return (step << 32) | (rank << 16) | (unit << 4) | k
+
+
 class Batch:
     """A micro-batch staged in HBM with its index bookkeeping precomputed (label shift,
     loss-row compaction, image-token map, the embedding backward's id segments): the step
@@ -292,6 +311,12 @@ def _check_labels(kept: np.ndarray, vocab_valid: int) -> None:
         raise ValueError(f"labels must be -100 or lie in [0, {vocab_valid})")
 
 
+def _dp_rank() -> int:
+    import torch.distributed as dist
+
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
 def _to(t: torch.Tensor, device: torch.device, dtype) -> torch.Tensor:
     """Asynchronous host-to-device staging (pinned when the loader pinned it)."""
     t = t.to(dtype).contiguous()
@@ -347,6 +372,20 @@ class Engine:
             store.transposed.append("text.embed")
         if self.frozen and not t.llama:
             raise NotImplementedError("freeze_tower_and_llm is the llava-pretrain (Llama) recipe")
+        # hidden dropout (cfg.text / cfg.vision .hidden_dropout; a frozen tower has none).  The
+        # masks are functions of (dropout_seed, dropout_site(micro-step, rank, unit, k)) and are
+        # never stored: the micro-step counter advances once per forward(need_grad=True) and is
+        # held for that step's backward and checkpoint recompute; accumulation micro-steps and
+        # data-parallel ranks draw other masks.  dropout_enabled = False is eval(): the p = 0 path
+        self.dropout_seed = 0
+        self.dropout_enabled = True
+        self.dropout_step = 0
+        self.rank = _dp_rank()
+        for layers in (t.layers, cfg.vision.used_layers if cfg.multimodal else 0):
+            if layers >= VISION_UNIT:
+                raise ValueError(f"{layers} layers: dropout_site numbers at most {VISION_UNIT - 1}")
+        self._pt = self._pv = 0.0  # the probabilities of the micro-step in flight
+        self._dstep = 0
         if store.device.type == "cuda":
             store.refresh_transposed()
 
@@ -575,6 +614,30 @@ class Engine:
                        inverse=inverse, parts=parts, offset=offset,
                        pos=None if self._vl is None else self._vl.pos)
 
+    # -------------------------------------------------------------- hidden dropout
+    def _site(self, unit: int, k: int) -> int:
+        return dropout_site(self._dstep, self.rank, unit, k)
+
+    def _drop_begin(self, need_grad: bool) -> None:
+        """Fix the micro-step's dropout state (probabilities, mask counter) for the forward, its
+        backward and any recompute.  A forward without gradients previews the next step's masks
+        and leaves the counter alone."""
+        on = self.dropout_enabled
+        self._pt = self.cfg.text.hidden_dropout if on else 0.0
+        self._pv = self.cfg.vision.hidden_dropout if on and self.cfg.multimodal and \
+            not self.frozen else 0.0
+        self._dstep = self.dropout_step
+        if need_grad and (self._pt > 0 or self._pv > 0):
+            self.dropout_step += 1
+
+    def _drop_grad(self, d, p, unit, k, bias, out=None):
+        """A dropped branch's gradient drop(d) (same site as the forward; in place unless `out`)
+        and its Linear's bias gradient: the column sum of the masked gradient."""
+        out = d if out is None else out
+        K.dropout_bf16(d, out, p, self.dropout_seed, self._site(unit, k))
+        K.colsum(out, self.s.g(bias), accumulate=True)
+        return out
+
     def _text_layer_fwd(self, i, x, B, S):
         t = self.cfg.text
         T, h, H, D = x.shape[0], t.hidden, t.heads, t.head_dim
@@ -599,7 +662,12 @@ class Engine:
         self._linear(y2, p + "fc1", out=pre, epi=K.EPI_BF16_GELU, out2=act)
         xn = self._e(T, h, dtype=F32)
         # h' = (mlp + attn) [bf16 add] + h [fp32]   (tf:modeling_gpt_neox.py:271-274)
-        self._linear(act, p + "fc2", out=xn, epi=K.EPI_F32_RESID, aux=ap, out2=x)
+        if self._pt > 0:  # h' = bf16(drop(mlp) + drop(attn)) + h: post_mlp / post_attention_dropout
+            mlp = self._linear(act, p + "fc2")
+            K.dropout_add_f32(ap, self._site(1 + i, 0), x, xn, self._pt, self.dropout_seed,
+                              y2=mlp, site_y2=self._site(1 + i, 1))
+        else:
+            self._linear(act, p + "fc2", out=xn, epi=K.EPI_F32_RESID, aux=ap, out2=x)
         if self.checkpointing and not self._recomputing:
             self.cache[("t", i)] = ("ckpt", x)
         else:
@@ -614,6 +682,8 @@ class Engine:
         p = f"text.layers.{i}."
         self._grad_open(f"text.layers.{i}")
         T = self._T
+        if self._pt > 0:  # the two biases then see differently masked gradients (_drop_grad)
+            return dict(dx_bf16=self._e(T, self.cfg.text.hidden))
         return dict(dx_bf16=self._e(T, self.cfg.text.hidden), dsum=self.s.g(p + "fc2.bias"),
                     dsum2=self.s.g(p + "dense.bias"))
 
@@ -628,12 +698,16 @@ class Engine:
         self._unit_bwd(f"text.layers.{i}")
         self._restore(("t", i), self._text_layer_fwd, i, B, S)
         x, mean, rstd, y1, y2, qkv, a, lse, pre, act = self.cache.pop(("t", i))
+        dsa = ds  # the gradients of the dense (attention) and fc2 (MLP) outputs
+        if self._pt > 0:  # each branch: drop(bf16(d residual)) with the forward's site
+            dsa = self._drop_grad(ds, self._pt, 1 + i, 0, p + "dense.bias", out=self._e(T, h))
+            ds = self._drop_grad(ds, self._pt, 1 + i, 1, p + "fc2.bias")
         dpre = self._dx_dgelu(ds, p + "fc2", pre, bias_of=p + "fc1")
         self._dw(ds, act, p + "fc2", bias=False)
         dy2 = self._dx(dpre, p + "fc1")
         self._dw(dpre, y2, p + "fc1", bias=False)
-        da = self._dx(ds, p + "dense")
-        self._dw(ds, a, p + "dense", bias=False)
+        da = self._dx(dsa, p + "dense")
+        self._dw(dsa, a, p + "dense", bias=False)
         dqkv = self._e(T, 3 * h)
         vl = self._vl
         if vl is not None:  # varlen: ring dK/dV + recomputing dQ, then the positional rope
@@ -743,14 +817,25 @@ class Engine:
         a = self._e(T, h)
         lse = self._e(B * H * Sv, dtype=F32)
         K.attention_fwd(qkv, B, Sv, H, D, D, h, False, D ** -0.5, a, lse)
-        h1 = self._linear(a, p + "o", epi=K.EPI_F32_RESID, out2=x)
+        pv, u = self._pv, VISION_UNIT + 1 + i
+        if pv > 0:  # h1 = x + drop(o): ViTSelfOutput.dropout
+            h1 = self._e(T, h, dtype=F32)
+            K.dropout_add_f32(self._linear(a, p + "o"), self._site(u, 0), x, h1, pv,
+                              self.dropout_seed)
+        else:
+            h1 = self._linear(a, p + "o", epi=K.EPI_F32_RESID, out2=x)
         y2 = self._e(T, h)
         m2, r2 = self._e(T, dtype=F32), self._e(T, dtype=F32)
         K.layernorm_fwd(h1, self.s.p(p + "ln2.weight"), self.s.p(p + "ln2.bias"), v.eps, y2, m2, r2)
         pre, act = self._e(T, v.ffn), self._e(T, v.ffn)
         self._linear(y2, p + "fc1", out=pre, out2=act,
                      epi=K.EPI_BF16_QGELU if v.act == "quick_gelu" else K.EPI_BF16_GELU)
-        xn = self._linear(act, p + "fc2", epi=K.EPI_F32_RESID, out2=h1)
+        if pv > 0:  # x' = h1 + drop(fc2): ViTOutput.dropout
+            xn = self._e(T, h, dtype=F32)
+            K.dropout_add_f32(self._linear(act, p + "fc2"), self._site(u, 1), h1, xn, pv,
+                              self.dropout_seed)
+        else:
+            xn = self._linear(act, p + "fc2", epi=K.EPI_F32_RESID, out2=h1)
         if self.frozen:
             pass  # frozen tower: no backward through it, nothing to keep
         elif self.checkpointing and not self._recomputing:
@@ -769,6 +854,9 @@ class Engine:
         self._unit_bwd(f"vision.layers.{i}")
         self._restore(("v", i), self._vit_layer_fwd, i, B, Sv)
         x, m1, r1, y1, qkv, a, lse, h1, m2, r2, y2, pre, act = self.cache.pop(("v", i))
+        pv, u = self._pv, VISION_UNIT + 1 + i
+        if pv > 0:  # d2 arrives unmasked and without fc2.bias's gradient
+            d2 = self._drop_grad(d2, pv, u, 1, p + "fc2.bias")
         dpre = self._dx_dgelu(d2, p + "fc2", pre, bias_of=p + "fc1", quick=v.act == "quick_gelu")
         self._dw(d2, act, p + "fc2", bias=False)
         dy2 = self._dx(dpre, p + "fc1")
@@ -777,7 +865,9 @@ class Engine:
         d1 = self._e(T, h)
         K.layernorm_bwd(h1, m2, r2, dy2, self.s.p(p + "ln2.weight"), dxn,
                         self.s.g(p + "ln2.weight"), self.s.g(p + "ln2.bias"), dresid=dxn,
-                        dx_bf16=d1, dsum=self.s.g(p + "o.bias"))
+                        dx_bf16=d1, dsum=None if pv > 0 else self.s.g(p + "o.bias"))
+        if pv > 0:
+            self._drop_grad(d1, pv, u, 0, p + "o.bias")
         da = self._dx(d1, p + "o")
         self._dw(d1, a, p + "o", bias=False)
         dqkv = self._e(T, 3 * h)
@@ -788,6 +878,8 @@ class Engine:
             self._grad_open(f"vision.layers.{i - 1}")
         nxt = {} if i == 0 else dict(dx_bf16=self._e(T, h),
                                      dsum=self.s.g(f"vision.layers.{i - 1}.fc2.bias"))
+        if pv > 0:
+            nxt.pop("dsum", None)
         K.layernorm_bwd(x, m1, r1, dy1, self.s.p(p + "ln1.weight"), dxn,
                         self.s.g(p + "ln1.weight"), self.s.g(p + "ln1.bias"), dresid=dxn, **nxt)
         self._unit_done(f"vision.layers.{i}")
@@ -803,6 +895,8 @@ class Engine:
         h = self._e(B * (npch + 1), hv, dtype=F32)
         self._f32_fwd("vision.pos")
         K.vit_embed_fwd(B, npch, po, self.s.p("vision.cls"), self.s.p("vision.pos"), h)
+        if self._pv > 0:  # ViTEmbeddings.dropout, after the position add
+            K.dropout_f32(h, h, self._pv, self.dropout_seed, self._site(VISION_UNIT, 0))
         pre_ln = None
         if v.pre_ln:  # CLIP pre_layrnorm: fp32 in, fp32 residual stream out
             e = h
@@ -845,7 +939,8 @@ class Engine:
         self._grad_open(f"vision.layers.{top}")
         d2 = self._e(B * (npch + 1), hv)
         K.cast_f32_bf16(dh, d2)
-        K.colsum(d2, self.s.g(f"vision.layers.{top}.fc2.bias"), accumulate=True)
+        if self._pv == 0:  # else the layer sums its masked gradient itself
+            K.colsum(d2, self.s.g(f"vision.layers.{top}.fc2.bias"), accumulate=True)
         for i in reversed(range(v.used_layers)):
             dh, d2 = self._vit_layer_bwd(i, dh, d2, B, npch + 1)
         if pre_ln is not None:  # through pre_layrnorm (its γ/β grads accumulate)
@@ -854,6 +949,8 @@ class Engine:
             K.layernorm_f32_bwd(e, m0, r0, dh, self.s.p("vision.ln_pre.weight"), de,
                                 self.s.g("vision.ln_pre.weight"), self.s.g("vision.ln_pre.bias"))
             dh = de
+        if self._pv > 0:
+            K.dropout_f32(dh, dh, self._pv, self.dropout_seed, self._site(VISION_UNIT, 0))
         dpo = self._e(B * npch, hv)
         self._f32_bwd("vision.pos")
         K.vit_embed_bwd(B, npch, dh, self.s.g("vision.cls"), self.s.g("vision.pos"), dpo)
@@ -877,10 +974,13 @@ class Engine:
             region()
         if S > self.cos.shape[0]:
             raise ValueError(f"sequence {S} longer than the rope table {self.cos.shape[0]}")
+        self._drop_begin(need_grad)
         img = self._vision_fwd(batch.pixels, B) if cfg.multimodal else None
         h = self._e(T, t.hidden, dtype=F32)
         self._f32_fwd("text.embed")
         K.embed_fwd(batch.ids, self.s.p("text.embed"), h, batch.img_map, img)
+        if self._pt > 0:  # GPTNeoX emb_dropout, after the image-token merge
+            K.dropout_f32(h, h, self._pt, self.dropout_seed, self._site(0, 0))
         layer_fwd = self._llama_layer_fwd if t.llama else self._text_layer_fwd
         for i in range(t.layers):
             self._unit_fwd(f"text.layers.{i}")
@@ -950,6 +1050,8 @@ class Engine:
             dh, ds = layer_bwd(i, dh, ds, B, S)
             self._ready((f"text.layers.{i}.",))
         dimg = self._e(B * cfg.vision.num_patches, t.hidden) if cfg.multimodal else None
+        if self._pt > 0:
+            K.dropout_f32(dh, dh, self._pt, self.dropout_seed, self._site(0, 0))
         self._f32_bwd("text.embed")
         K.embed_bwd(batch.segments, dh, None if self.frozen else self.s.g("text.embed"),
                     batch.img_map, dimg)

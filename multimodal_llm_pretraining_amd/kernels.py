@@ -591,6 +591,63 @@ def cast_f32_bf16(src, dst) -> None:
     _lib.call("mmpt_cast_f32_bf16", src.numel(), src.data_ptr(), dst.data_ptr(), _stream())
 
 
+# ----------------------------------------------------------------------------- dropout
+# Hidden dropout with the masks recomputed from (seed, site) by a counter-based generator
+# (include/mmpt.h K16): seed and site are unsigned 64-bit integers, p a Python float in [0, 1).
+_U64 = (1 << 64) - 1
+
+
+def dropout_bf16(src, dst, p: float, seed: int, site: int) -> None:
+    """dst = keep ? bf16(f32(src) * 1/(1-p)) : 0 over a 2-D bf16 tensor (dst may be src); the
+    mask follows the logical index row*h + col whatever the row strides.  Forward and backward."""
+    _check(src, torch.bfloat16, "dropout_bf16.src")
+    _check(dst, torch.bfloat16, "dropout_bf16.dst")
+    rows, h = src.shape
+    if tuple(dst.shape) != (rows, h):
+        raise ValueError("dropout_bf16: dst shape differs from src")
+    _lib.call("mmpt_dropout_bf16", rows, h, src.data_ptr(), _ld(src), dst.data_ptr(), _ld(dst),
+              float(p), seed & _U64, site & _U64, _stream())
+
+
+def dropout_f32(src, dst, p: float, seed: int, site: int) -> None:
+    """The same on dense fp32 [rows, h] (the embedding outputs and their gradients)."""
+    _check(src, torch.float32, "dropout_f32.src")
+    _check(dst, torch.float32, "dropout_f32.dst")
+    rows, h = src.shape
+    if tuple(dst.shape) != (rows, h) or not (src.is_contiguous() and dst.is_contiguous()):
+        raise ValueError("dropout_f32: src and dst must be dense [rows, h] of one shape")
+    _lib.call("mmpt_dropout_f32", rows, h, src.data_ptr(), dst.data_ptr(), float(p), seed & _U64,
+              site & _U64, _stream())
+
+
+def dropout_add_f32(y, site_y: int, resid, out, p: float, seed: int, y2=None,
+                    site_y2: int = 0) -> None:
+    """out = resid + f32(v), v = drop(y) or, with y2, bf16(drop(y2) + drop(y)); y, y2 bf16,
+    resid / out dense fp32 (out may be resid)."""
+    _check(y, torch.bfloat16, "dropout_add_f32.y")
+    _check(resid, torch.float32, "dropout_add_f32.resid")
+    _check(out, torch.float32, "dropout_add_f32.out")
+    rows, h = y.shape
+    if y2 is not None:
+        _check(y2, torch.bfloat16, "dropout_add_f32.y2")
+    for t in (resid, out) + (() if y2 is None else (y2,)):
+        if tuple(t.shape) != (rows, h):
+            raise ValueError("dropout_add_f32: shapes differ")
+    if not (resid.is_contiguous() and out.is_contiguous()):
+        raise ValueError("dropout_add_f32: resid and out must be dense")
+    _lib.call("mmpt_dropout_add_f32", rows, h, y.data_ptr(), _ld(y), site_y & _U64, _p(y2),
+              0 if y2 is None else _ld(y2), site_y2 & _U64, resid.data_ptr(), out.data_ptr(),
+              float(p), seed & _U64, _stream())
+
+
+def dropout_mask(n: int, p: float, seed: int, site: int, device=None) -> torch.Tensor:
+    """uint8 [n]: the keep bits of the logical elements 0 .. n-1 of a site (test hook)."""
+    keep = torch.empty(n, dtype=torch.uint8, device="cuda" if device is None else device)
+    _lib.call("mmpt_dropout_mask", n, float(p), seed & _U64, site & _U64, keep.data_ptr(),
+              _stream())
+    return keep
+
+
 def transpose_bf16_batched(src_flat, dst_flat, desc, total_tiles: int) -> None:
     """Every weight's W^T in one launch: desc = device int64 [n, 4] {offset, rows, cols,
     first tile} into the flat bf16 buffers src_flat / dst_flat."""

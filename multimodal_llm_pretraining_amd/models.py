@@ -290,6 +290,7 @@ class MMPTForPretraining(nn.Module):
                                 trainable=cfg.trainable if cfg.freeze_tower_and_llm else None)
         init_normal(self.store, seed, cfg=cfg)
         self.engine = Engine(cfg, self.store)
+        self.set_dropout_seed(seed)
         self._plist: list[nn.Parameter] = []
         for name in self.store.names():
             parent = self
@@ -326,6 +327,13 @@ class MMPTForPretraining(nn.Module):
     def gradient_checkpointing_disable(self):
         self.gradient_checkpointing = False
         self.engine.checkpointing = False
+
+    def set_dropout_seed(self, seed: int) -> None:
+        """Key of the hidden-dropout masks (cfg.text / cfg.vision .hidden_dropout; default: the
+        constructor's `seed`).  Dropout is active iff the module is in train() mode and p > 0;
+        the masks also depend on the micro-step counter and the data-parallel rank
+        (engine.dropout_site)."""
+        self.engine.dropout_seed = int(seed)
 
     # -- ZeRO-3 hand-over
     def partition_out(self) -> dict[str, torch.Tensor]:
@@ -375,6 +383,7 @@ class MMPTForPretraining(nn.Module):
         if labels is None:
             raise ValueError("the pre-training step needs labels (loss is the output)")
         self._refresh_if_stale()
+        self.engine.dropout_enabled = self.training  # eval() switches hidden dropout off
         # a right-padded mask (the reference collators' padding=True) drops the pad tokens:
         # the step runs over the valid tokens only (Batch); other mask shapes raise ValueError
         batch = Batch(self.mmpt_config, input_ids, labels, pixel_values, self.store.device,
@@ -399,7 +408,7 @@ def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
                        rotary_pct=t.rotary_pct, rotary_emb_base=t.rope_theta,
                        max_position_embeddings=2048, use_parallel_residual=True,
                        hidden_act="gelu", layer_norm_eps=t.eps, tie_word_embeddings=False,
-                       attn_implementation="eager")
+                       hidden_dropout=t.hidden_dropout, attn_implementation="eager")
     if cfg.vision is None:
         return GPTNeoXForCausalLM(tc)
     from transformers import LlavaConfig, LlavaForConditionalGeneration, ViTConfig
@@ -407,7 +416,7 @@ def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
     v = cfg.vision
     vc = ViTConfig(hidden_size=v.hidden, num_hidden_layers=v.layers, num_attention_heads=v.heads,
                    intermediate_size=v.ffn, image_size=v.image, patch_size=v.patch,
-                   attn_implementation="eager")
+                   hidden_dropout_prob=v.hidden_dropout, attn_implementation="eager")
     lc = LlavaConfig(vision_config=vc, text_config=tc, image_token_id=cfg.image_token_id,
                      vision_feature_layer=v.feature_layer,
                      vision_feature_select_strategy="default", projector_hidden_act="gelu")

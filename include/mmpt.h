@@ -463,6 +463,36 @@ int mmpt_dropout_mask(int64_t n, double p, uint64_t seed, uint64_t site, uint8_t
                       void* stream);
 
 /* ------------------------------------------------------------------------
+ * K18  classification head: ViTForImageClassification (tf:models/vit/modeling_vit.py,
+ * ViTModel(add_pooling_layer=False).layernorm then `classifier(sequence_output[:, 0, :])`).
+ * HF runs vit.layernorm (fp32 under autocast) over every token and reads only the CLS row; these
+ * entries compute that row alone.  The classifier itself is K1 (bias epilogue) and the loss the
+ * cross entropy with `vocab_valid` = the label count (the head padded to a multiple of 8 rows).
+ * Added without a change of MMPT_ABI_VERSION: the entries are new, nothing existing changed.
+ * h % 8 == 0 (and h <= 4096), 16-B aligned pointers, leading dimensions multiples of 8 and
+ * >= h, batch * tokens < 2^31; else MMPT_ERR_ARG.
+ * ---------------------------------------------------------------------- */
+/* y[b] = bf16(LN(x[b*tokens]; w, b)) for the CLS row of each of `batch` samples;
+ * x fp32 dense [batch*tokens][h]; y bf16 [batch][ld_y]; mean, rstd fp32 [batch].  The bits of
+ * mmpt_layernorm_fwd on a dense copy of those rows. */
+int mmpt_cls_ln_fwd(int64_t batch, int64_t tokens, int64_t h, float eps, const float* x,
+                    const float* w, const float* b, void* y, int64_t ld_y, float* mean,
+                    float* rstd, void* stream);
+int64_t mmpt_cls_ln_bwd_workspace_bytes(int64_t batch, int64_t h);
+/* One pass writes EVERY row of dx (fp32 dense [batch*tokens][h]) and, if non-NULL, of dx_bf16
+ * (bf16, same shape): row b*tokens = LN'(dy[b]; w), every other row +0 (the gradient of the
+ * residual stream is non-zero on the CLS rows only) — no memset, scatter or cast beside it.
+ * dy bf16 [batch][ld_dy].  dw, db (nullable) accumulate (+=).  dsum (nullable, needs dx_bf16) +=
+ * f32(bf16(Σ_b bf16(dx[b*tokens]))): the top encoder layer's output-bias gradient.  Fixed-order
+ * reductions, no atomics: the CLS rows, dw, db and dsum carry the bits of
+ * mmpt_layernorm_bwd_ex(rows = batch) on a dense copy of the CLS rows.
+ * `workspace` >= mmpt_cls_ln_bwd_workspace_bytes. */
+int mmpt_cls_ln_bwd(int64_t batch, int64_t tokens, int64_t h, const float* x, const float* mean,
+                    const float* rstd, const void* dy, int64_t ld_dy, const float* w, float* dx,
+                    void* dx_bf16, float* dw, float* db, float* dsum, void* workspace,
+                    void* stream);
+
+/* ------------------------------------------------------------------------
  * ZeRO++ quantized communication (sharding = "zero_3++"): replaces DeepSpeed's
  * `zero_quantized_weights` / `zero_quantized_gradients` kernels that
  * src/train.py:196-201 switches on.  Blockwise symmetric quantization, 256-element

@@ -83,6 +83,11 @@ class ManualTrainer:
                               scheduler=getattr(tc.scheduler_type, "value", tc.scheduler_type),
                               num_warmup_steps=warm, num_training_steps=tc.num_training_steps,
                               min_lr_rate=sched_kw.get("min_lr_rate", 0.0))
+        if sharding_to_mode(sharding) in ("zero2", "zero3") and model.mmpt_config.classifier:
+            raise NotImplementedError(  # before partition_out releases the module's storage
+                f"sharding {sharding!r} for the vision-only classifier "
+                f"{C.preset_name(model.mmpt_config)!r} is not implemented (data parallel and "
+                "zero_1 are)")
         if sharding_to_mode(sharding) in ("zero2", "zero3") and \
                 not model.mmpt_config.freeze_tower_and_llm:
             # ZeRO-2/3 partition the fp32 master, gradients and optimizer state (ZeRO-3 the
@@ -205,6 +210,8 @@ def count_flops_per_example(model_class) -> float:
     eager model (full-square attention).  Restated analytically (config.flops_per_sample):
     3 × forward matmul FLOPs at the model class's sequence length."""
     cfg = model_class.model_config
+    if cfg.classifier:  # one image per example: no sequence length
+        return C.flops_per_sample(cfg, 0)
     n_img = cfg.vision.num_patches if cfg.vision is not None else 0
     return C.flops_per_sample(cfg, model_class.sequence_length - n_img)
 

@@ -123,17 +123,43 @@ class TextConfig:
 
 @dataclass(frozen=True)
 class ModelConfig:
-    text: TextConfig
+    """text + optional vision tower: a language model or a LLaVA composition.  text = None
+    with num_classes > 0: a vision-only classifier (ViTForImageClassification,
+    tf:models/vit/modeling_vit.py: the encoder, vit.layernorm, the CLS row, a Linear head)."""
+
+    text: TextConfig | None = None
     vision: VisionConfig | None = None
     image_token_id: int = 50303  # last id of the 50304 Pythia vocab (SURVEY P11)
     # LLaVA-pretrain freeze (src/models/llava.py:49-52, under the pinned transformers 4.47.1
     # names): the vision tower and the whole language model (embeddings, layers, final norm,
     # lm_head) are frozen — only the projector is trained.
     freeze_tower_and_llm: bool = False
+    num_classes: int = 0  # > 0 (with text = None): the classification head's labels
+
+    def __post_init__(self):
+        if self.text is None:
+            if self.vision is None or self.num_classes <= 0:
+                raise ValueError("a model without a text model is a vision-only classifier: it "
+                                 "needs a vision tower and num_classes > 0")
+            if self.vision.pre_ln or self.freeze_tower_and_llm:
+                raise ValueError("the classifier is ViTForImageClassification: a ViT tower "
+                                 "(no pre_ln), nothing frozen")
+        elif self.num_classes:
+            raise ValueError("num_classes > 0 needs text = None (a vision-only classifier)")
 
     @property
     def multimodal(self) -> bool:
         return self.vision is not None
+
+    @property
+    def classifier(self) -> bool:
+        return self.text is None
+
+    @property
+    def classes_padded(self) -> int:
+        """num_classes rounded up to a multiple of 8 (16-B GEMM rows): the pad rows of the head
+        are zero, take no part in the softmax (vocab_valid) and keep a zero gradient."""
+        return (self.num_classes + 7) // 8 * 8
 
     def trainable(self, name: str) -> bool:
         return not self.freeze_tower_and_llm or name.startswith("proj.")
@@ -197,6 +223,17 @@ PRESETS["tiny-mm"] = ModelConfig(
 PRESETS["tiny-mm-drop"] = ModelConfig(
     text=replace(PRESETS["tiny-mm"].text, hidden_dropout=0.1),
     vision=replace(PRESETS["tiny-mm"].vision, hidden_dropout=0.1), image_token_id=1023)
+# vision-only classifiers: the reference's `vit` (src/models/vit.py: ViT-L/16-224 in21k config,
+# 21,841 labels, hidden_dropout_prob 0.1) and tiny forms for the parity tests (17 tokens per
+# image, 1001 classes padded to 1008)
+VIT_L16_CLS = VisionConfig(hidden=1024, layers=24, heads=16, ffn=4096, image=224, patch=16,
+                           eps=1e-12, hidden_dropout=0.1, feature_layer=-1)
+PRESETS["vit-l16-cls"] = ModelConfig(vision=VIT_L16_CLS, num_classes=21841)
+PRESETS["tiny-vit-cls"] = ModelConfig(
+    vision=VisionConfig(hidden=128, layers=3, heads=2, ffn=256, image=64, patch=16,
+                        feature_layer=-1), num_classes=1001)
+PRESETS["tiny-vit-cls-drop"] = ModelConfig(
+    vision=replace(PRESETS["tiny-vit-cls"].vision, hidden_dropout=0.1), num_classes=1001)
 PRESETS["tiny-lm"] = ModelConfig(text=TextConfig(hidden=256, layers=2, heads=2, ffn=512, vocab=512))
 # Pythia-2.8B's head shape (head_dim 80 -> padded D = 128 attention, 20 rotary dims)
 PRESETS["tiny-lm-d80"] = ModelConfig(text=TextConfig(hidden=320, layers=2, heads=4, ffn=640,
@@ -231,6 +268,10 @@ def with_dropout(cfg: ModelConfig, text: float = 0.0, vision: float = 0.0) -> Mo
         if vision > 0:
             raise ValueError("vision hidden_dropout > 0 on a model without a vision tower")
         return replace(cfg, text=replace(cfg.text, hidden_dropout=text))
+    if cfg.text is None:
+        if text > 0:
+            raise ValueError("text hidden_dropout > 0 on a model without a text model")
+        return replace(cfg, vision=replace(cfg.vision, hidden_dropout=vision))
     return replace(cfg, text=replace(cfg.text, hidden_dropout=text),
                    vision=replace(cfg.vision, hidden_dropout=vision))
 
@@ -240,6 +281,11 @@ def get_config(name: str) -> ModelConfig:
         return PRESETS[name]
     except KeyError as e:
         raise ValueError(f"unknown model {name!r}; known: {sorted(PRESETS)}") from e
+
+
+def preset_name(cfg: ModelConfig) -> str | None:
+    """The PRESETS key of a configuration (None: not a preset) — for messages."""
+    return next((n for n, c in PRESETS.items() if c == cfg), None)
 
 
 def param_shapes(cfg: ModelConfig) -> dict[str, tuple[int, ...]]:
@@ -270,6 +316,12 @@ def param_shapes(cfg: ModelConfig) -> dict[str, tuple[int, ...]]:
             s[p + "fc1.bias"] = (v.ffn,)
             s[p + "fc2.weight"] = (v.hidden, v.ffn)
             s[p + "fc2.bias"] = (v.hidden,)
+        if cfg.classifier:  # vit.layernorm + classifier (pad rows: classes_padded)
+            s["vision.ln_post.weight"] = (v.hidden,)
+            s["vision.ln_post.bias"] = (v.hidden,)
+            s["cls_head.weight"] = (cfg.classes_padded, v.hidden)
+            s["cls_head.bias"] = (cfg.classes_padded,)
+            return s
         s["proj.fc1.weight"] = (t.hidden, v.hidden)
         s["proj.fc1.bias"] = (t.hidden,)
         s["proj.fc2.weight"] = (t.hidden, t.hidden)
@@ -318,6 +370,17 @@ def num_params(cfg: ModelConfig) -> int:
     return n
 
 
+def _classifier_flops(cfg: ModelConfig) -> float:
+    """3 × (patch GEMM + every layer + the head's 2·hidden·num_classes): every layer is used
+    and the attention is non-causal, so the executed count is the reference-convention one."""
+    v = cfg.vision
+    Sv = v.num_patches + 1
+    fwd = 2 * v.num_patches * v.hidden * v.channels * v.patch ** 2
+    fwd += v.layers * (2 * Sv * v.hidden * (4 * v.hidden + 2 * v.ffn) + 4 * Sv * Sv * v.hidden)
+    fwd += 2 * v.hidden * cfg.num_classes
+    return 3.0 * fwd
+
+
 def flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     """Algorithmic fwd+bwd FLOPs per sample in the reference's convention
     (src/benchmarking/flops.py:9-37: FlopCounterMode over one fwd+bwd, eager
@@ -326,6 +389,8 @@ def flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     With `freeze_tower_and_llm` (llava-pretrain, src/models/llava.py:49-52) autograd runs no
     backward in the vision tower and no weight gradients in the LLM: the count is then
     vision 1× + LLM linears 2× (forward + input gradient) + attention 3× + projector 3×."""
+    if cfg.classifier:
+        return _classifier_flops(cfg)
     t = cfg.text
     S = seq_text + (cfg.vision.num_patches if cfg.vision else 0)
     if t.llama:  # q,o: h^2 each; k,v: h*kv_dim each; gate, up, down: h*F each
@@ -355,6 +420,8 @@ def executed_flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     over the lower triangle with the diagonal (S(S+1)/2 score/PV pairs per head instead of
     S²), and only the vision layers the model reads (`used_layers`: vision_feature_layer
     -2 leaves the last one unbuilt).  Non-causal ViT attention stays square."""
+    if cfg.classifier:
+        return _classifier_flops(cfg)
     t = cfg.text
     n_img = cfg.vision.num_patches if cfg.vision else 0
     S = seq_text + n_img

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(int rows, int h, float eps,
                                                      const float* __restrict__ b1, bf16_t* y1,
                                                      const float* __restrict__ w2,
                                                      const float* __restrict__ b2, bf16_t* y2,
-                                                     float* mean_out, float* rstd_out) {
+                                                     float* mean_out, float* rstd_out, long ldy) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * LN_WAVES + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -65,12 +65,12 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(int rows, int h, float eps,
     uint2 o;
     o.x = (uint32_t)f2bf(xh[0] * g.x + bb.x) | ((uint32_t)f2bf(xh[1] * g.y + bb.y) << 16);
     o.y = (uint32_t)f2bf(xh[2] * g.z + bb.z) | ((uint32_t)f2bf(xh[3] * g.w + bb.w) << 16);
-    ((uint2*)(y1 + (long)row * h))[i] = o;
+    ((uint2*)(y1 + (long)row * ldy))[i] = o;
     if (y2 != nullptr) {
       const float4 g2 = ((const float4*)w2)[i], c2 = ((const float4*)b2)[i];
       o.x = (uint32_t)f2bf(xh[0] * g2.x + c2.x) | ((uint32_t)f2bf(xh[1] * g2.y + c2.y) << 16);
       o.y = (uint32_t)f2bf(xh[2] * g2.z + c2.z) | ((uint32_t)f2bf(xh[3] * g2.w + c2.w) << 16);
-      ((uint2*)(y2 + (long)row * h))[i] = o;
+      ((uint2*)(y2 + (long)row * ldy))[i] = o;
     }
   }
 }
@@ -479,6 +479,116 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce(int nblk, int h, const floa
   if (wave == 0 && c < h && dst) dst[c] += (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
 }
 
+// K18: the classification head's LayerNorm backward (ViTForImageClassification reads only
+// the CLS row of vit.layernorm's output).  One launch: workgroups [0, nblk) run
+// ln_bwd_rows_kernel's row arithmetic, op for op, on the CLS rows (x / dx row b*tokens, dy row
+// b) and leave the same [block][5][h] partials for ln_rows_reduce; the workgroups after them
+// store +0 over every other row of dx and dx_bf16 (16-B vector stores), so the dense gradient
+// of the residual stream and its bf16 copy come out of one pass with no memset before it.
+#ifndef MMPT_CLS_ZERO_BLOCKS
+#define MMPT_CLS_ZERO_BLOCKS 2048
+#endif
+template <int PT>
+__global__ __launch_bounds__(256) void cls_ln_bwd_kernel(
+    int batch, int tokens, int h, int nblk, const float* __restrict__ x,
+    const float* __restrict__ mean, const float* __restrict__ rstd, const bf16_t* __restrict__ dy1,
+    long ld_dy, const float* __restrict__ w1, float* dx, bf16_t* __restrict__ dxb, int want_dsum,
+    float* __restrict__ partials) {
+  __shared__ float red[2][4][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nv = h >> 2;
+  if ((int)blockIdx.x >= nblk) {  // the zero rows: every row r with r % tokens != 0
+    const long total = (long)batch * tokens;
+    const int nz = gridDim.x - nblk, n8 = h >> 3;
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint4 z8 = make_uint4(0u, 0u, 0u, 0u);
+    for (long r = blockIdx.x - nblk; r < total; r += nz) {
+      if (r % tokens == 0) continue;
+      float4* d4 = (float4*)(dx + r * h);
+      for (int i = tid; i < nv; i += 256) d4[i] = z4;
+      if (dxb != nullptr) {
+        uint4* d8 = (uint4*)(dxb + r * h);
+        for (int i = tid; i < n8; i += 256) d8[i] = z8;
+      }
+    }
+    return;
+  }
+  float4 aw1[PT], ab1[PT], as[PT];
+  float4 ww1[PT];
+#pragma unroll
+  for (int j = 0; j < PT; ++j) {
+    aw1[j] = ab1[j] = as[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int i = j * 256 + tid;
+    ww1[j] = i < nv ? ((const float4*)w1)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  int par = 0;
+  for (int row = blockIdx.x; row < batch; row += nblk, par ^= 1) {
+    const float mu = mean[row], rs = rstd[row];
+    const long xrow = (long)row * tokens * h;
+    const float4* xr = (const float4*)(x + xrow);
+    float4 xh[PT], g1[PT];
+    float s1a = 0.f, s1b = 0.f;
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
+      const int i = j * 256 + tid;
+      xh[j] = g1[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (i >= nv) continue;
+      const float4 xv = xr[i];
+      xh[j] = make_float4((xv.x - mu) * rs, (xv.y - mu) * rs, (xv.z - mu) * rs, (xv.w - mu) * rs);
+      const float4 d1 = ld_bf16x4(dy1 + (long)row * ld_dy + i * 4);
+      g1[j] = make_float4(d1.x * ww1[j].x, d1.y * ww1[j].y, d1.z * ww1[j].z, d1.w * ww1[j].w);
+      s1a += (g1[j].x * xh[j].x + g1[j].y * xh[j].y) + (g1[j].z * xh[j].z + g1[j].w * xh[j].w);
+      s1b += (g1[j].x + g1[j].y) + (g1[j].z + g1[j].w);
+      aw1[j].x += d1.x * xh[j].x; aw1[j].y += d1.y * xh[j].y;
+      aw1[j].z += d1.z * xh[j].z; aw1[j].w += d1.w * xh[j].w;
+      ab1[j].x += d1.x; ab1[j].y += d1.y; ab1[j].z += d1.z; ab1[j].w += d1.w;
+    }
+    s1a = wave_sum(s1a);
+    s1b = wave_sum(s1b);
+    if (lane == 0) {
+      red[par][wave][0] = s1a;
+      red[par][wave][1] = s1b;
+    }
+    __syncthreads();
+    const float inv_h = 1.0f / (float)h;
+    const float c1a = ((red[par][0][0] + red[par][1][0]) + (red[par][2][0] + red[par][3][0])) * inv_h;
+    const float c1b = ((red[par][0][1] + red[par][1][1]) + (red[par][2][1] + red[par][3][1])) * inv_h;
+    float4* dxr = (float4*)(dx + xrow);
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
+      const int i = j * 256 + tid;
+      if (i >= nv) continue;
+      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+      o.x += rs * (g1[j].x - xh[j].x * c1a - c1b);
+      o.y += rs * (g1[j].y - xh[j].y * c1a - c1b);
+      o.z += rs * (g1[j].z - xh[j].z * c1a - c1b);
+      o.w += rs * (g1[j].w - xh[j].w * c1a - c1b);
+      dxr[i] = o;
+      if (dxb != nullptr) {
+        uint2 u;
+        u.x = (uint32_t)f2bf(o.x) | ((uint32_t)f2bf(o.y) << 16);
+        u.y = (uint32_t)f2bf(o.z) | ((uint32_t)f2bf(o.w) << 16);
+        ((uint2*)(dxb + xrow))[i] = u;
+        if (want_dsum) {
+          as[j].x += round_bf(o.x); as[j].y += round_bf(o.y);
+          as[j].z += round_bf(o.z); as[j].w += round_bf(o.w);
+        }
+      }
+    }
+  }
+  float4* out = (float4*)(partials + (long)blockIdx.x * 5 * h);
+#pragma unroll
+  for (int j = 0; j < PT; ++j) {
+    const int i = j * 256 + tid;
+    if (i >= nv) continue;
+    out[i] = aw1[j];
+    out[nv + i] = ab1[j];
+    if (want_dsum) out[4 * nv + i] = as[j];
+  }
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 template <int MAXJ>
 void launch_fwd(int rows, int h, float eps, const float* x, long ldx, const float* w1,
                 const float* b1, bf16_t* y1, const float* w2, const float* b2, bf16_t* y2,
@@ -490,7 +600,7 @@ void launch_fwd(int rows, int h, float eps, const float* x, long ldx, const floa
                                                                      y1, w2, b2, y2, mean, rstd);
     return;
   }
-  ln_fwd_kernel<MAXJ><<<nblk, 256, 0, s>>>(rows, h, eps, x, ldx, w1, b1, y1, w2, b2, y2, mean, rstd);
+  ln_fwd_kernel<MAXJ><<<nblk, 256, 0, s>>>(rows, h, eps, x, ldx, w1, b1, y1, w2, b2, y2, mean, rstd, h);
 }
 
 template <int MAXJ, bool DY32 = false>
@@ -683,7 +793,7 @@ extern "C" int mmpt_rmsnorm_fwd(int64_t rows, int64_t h, float eps, const float*
   const int r = (int)rows, hh = (int)h;
   bf16_t* o = (bf16_t*)y;
 #define MMPT_RMSF(J) ln_fwd_kernel<J, true><<<g, 256, 0, s>>>(r, hh, eps, x, ldx, w, nullptr, o, \
-                                                             nullptr, nullptr, nullptr, nullptr, rstd)
+                                                             nullptr, nullptr, nullptr, nullptr, rstd, hh)
   switch (mj) {
     case 1: MMPT_RMSF(1); break;
     case 2: MMPT_RMSF(2); break;
@@ -726,4 +836,74 @@ extern "C" int mmpt_rmsnorm_bwd(int64_t rows, int64_t h, const float* x, int64_t
   ln_rows_reduce<<<rg, 256, 0, s>>>(nblk, (int)h, part, dw, nullptr, nullptr, nullptr, nullptr,
                                     nullptr);
   return check_launch("rmsnorm_bwd_reduce");
+}
+
+// ---- K18: classification head (final LayerNorm on the CLS rows) ----
+extern "C" int mmpt_cls_ln_fwd(int64_t batch, int64_t tokens, int64_t h, float eps, const float* x,
+                               const float* w, const float* b, void* y, int64_t ld_y, float* mean,
+                               float* rstd, void* stream) {
+  MMPT_REQUIRE(batch > 0 && tokens > 0 && h > 0 && h % 8 == 0, "cls_ln_fwd: bad shape");
+  MMPT_REQUIRE(batch * tokens < (int64_t)1 << 31, "cls_ln_fwd: batch*tokens too large");
+  MMPT_REQUIRE(ld_y >= h && ld_y % 8 == 0, "cls_ln_fwd: ld_y must be a multiple of 8 and >= h");
+  MMPT_REQUIRE(x && w && b && y && mean && rstd, "cls_ln_fwd: null pointer");
+  MMPT_REQUIRE(aligned16(x) && aligned16(w) && aligned16(b) && aligned16(y),
+               "cls_ln_fwd: pointers must be 16-byte aligned");
+  const int mj = pick_maxj(h);
+  MMPT_REQUIRE(mj > 0, "cls_ln_fwd: h=%lld too large", (long long)h);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned g = (unsigned)((batch + LN_WAVES - 1) / LN_WAVES);
+  const int r = (int)batch, hh = (int)h;
+  const long ldx = (long)(tokens * h);
+  bf16_t* o = (bf16_t*)y;
+#define MMPT_CLSF(J) ln_fwd_kernel<J><<<g, 256, 0, s>>>(r, hh, eps, x, ldx, w, b, o, nullptr, nullptr, \
+                                                        nullptr, mean, rstd, (long)ld_y)
+  switch (mj) {
+    case 1: MMPT_CLSF(1); break;
+    case 2: MMPT_CLSF(2); break;
+    case 4: MMPT_CLSF(4); break;
+    case 8: MMPT_CLSF(8); break;
+    case 12: MMPT_CLSF(12); break;
+    default: MMPT_CLSF(16); break;
+  }
+#undef MMPT_CLSF
+  return check_launch("cls_ln_fwd");
+}
+
+extern "C" int64_t mmpt_cls_ln_bwd_workspace_bytes(int64_t batch, int64_t h) {
+  return mmpt_layernorm_bwd_ex_workspace_bytes(batch, h);
+}
+
+extern "C" int mmpt_cls_ln_bwd(int64_t batch, int64_t tokens, int64_t h, const float* x,
+                               const float* mean, const float* rstd, const void* dy, int64_t ld_dy,
+                               const float* w, float* dx, void* dx_bf16, float* dw, float* db,
+                               float* dsum, void* workspace, void* stream) {
+  MMPT_REQUIRE(batch > 0 && tokens > 0 && h > 0 && h % 8 == 0, "cls_ln_bwd: bad shape");
+  MMPT_REQUIRE(batch * tokens < (int64_t)1 << 31, "cls_ln_bwd: batch*tokens too large");
+  MMPT_REQUIRE(ld_dy >= h && ld_dy % 8 == 0, "cls_ln_bwd: ld_dy must be a multiple of 8 and >= h");
+  MMPT_REQUIRE(x && mean && rstd && dy && w && dx && workspace, "cls_ln_bwd: null pointer");
+  MMPT_REQUIRE(dsum == nullptr || dx_bf16, "cls_ln_bwd: dsum needs dx_bf16");
+  MMPT_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(w) && aligned16(dx) &&
+                   aligned16(dx_bf16) && aligned16(workspace),
+               "cls_ln_bwd: pointers must be 16-byte aligned");
+  const int64_t per = (h / 4 + 255) / 256;
+  MMPT_REQUIRE(per <= 4, "cls_ln_bwd: h=%lld too large", (long long)h);
+  const int nblk = (int)std::min<int64_t>(LNR_BLOCKS, batch);
+  const int nzero = (int)std::min<int64_t>(MMPT_CLS_ZERO_BLOCKS, batch * (tokens - 1));
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)workspace;
+  const bf16_t* d1 = (const bf16_t*)dy;
+  bf16_t* xb = (bf16_t*)dx_bf16;
+  const int ws = dsum != nullptr;
+#define MMPT_CLSB(PT) \
+  cls_ln_bwd_kernel<PT><<<nblk + nzero, 256, 0, s>>>((int)batch, (int)tokens, (int)h, nblk, x, mean, rstd, \
+                                                     d1, (long)ld_dy, w, dx, xb, ws, part)
+  if (per <= 1) MMPT_CLSB(1);
+  else if (per <= 2) MMPT_CLSB(2);
+  else MMPT_CLSB(4);
+#undef MMPT_CLSB
+  int rc = check_launch("cls_ln_bwd");
+  if (rc) return rc;
+  dim3 rg((unsigned)((h + 63) / 64), 5u);
+  ln_rows_reduce<<<rg, 256, 0, s>>>(nblk, (int)h, part, dw, db, nullptr, nullptr, dsum, nullptr);
+  return check_launch("cls_ln_bwd_reduce");
 }

@@ -1,5 +1,5 @@
 """Synthetic datasets of the benchmark (§8(a) row a15), restating
-src/benchmarking/data.py:8-21 (text) and :45-77 (multimodal).
+src/benchmarking/data.py:8-21 (text), :24-42 (image classification) and :45-77 (multimodal).
 
 Differences, both deliberate and documented in DESIGN.md:
 * samples are generated lazily and deterministically per index from (seed, index)
@@ -78,6 +78,30 @@ class DummyTextModelingDataset(Dataset):
         return {"input_ids": ids, "labels": ids.clone()}
 
 
+class DummyImageClassificationDataset(Dataset):
+    """src/benchmarking/data.py:24-42: pixels ~ U[0,1) [3, S, S], one label ~ U{0..C-1} per
+    image — generated per index from (seed, index), not as one [N, 3, S, S] tensor."""
+
+    def __init__(self, image_size: int, num_classes: int, num_samples: int = 20_000,
+                 seed: int = 0) -> None:
+        super().__init__()
+        if image_size < 1 or num_classes < 1:
+            raise ValueError("need image_size >= 1 and num_classes >= 1")
+        self.image_size, self.num_classes = image_size, num_classes
+        self.num_samples, self.seed = num_samples, seed
+
+    def __len__(self):
+        return self.num_samples
+
+    def __getitem__(self, index):
+        if not 0 <= index < self.num_samples:
+            raise IndexError(index)
+        g = _gen(self.seed, index)
+        pixels = torch.rand((3, self.image_size, self.image_size), generator=g)
+        label = torch.randint(0, self.num_classes, (), generator=g)
+        return {"pixel_values": pixels, "labels": label}
+
+
 class DummyMultimodalLanguageModelingDataset(Dataset):
     def __init__(self, vocab_size: int, sequence_length: int, image_size: int,
                  num_samples: int = 20_000, image_token_id: int = 32000, image_tokens: int = 1,
@@ -142,7 +166,8 @@ class PrefetchLoader:
         idx = [((self._next + i) * self.world + self.rank) % n for i in range(self.bs)]
         self._next += self.bs
         samples = [self.ds[i] for i in idx]
-        if len({s["input_ids"].numel() for s in samples}) > 1:  # variable-length samples
+        if "input_ids" in samples[0] and \
+                len({s["input_ids"].numel() for s in samples}) > 1:  # variable-length samples
             out = pad_collate(samples)
         else:
             out = {k: torch.stack([s[k] for s in samples]) for k in samples[0]}

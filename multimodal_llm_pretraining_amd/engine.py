@@ -15,6 +15,11 @@ tf:models/gpt_neox/modeling_gpt_neox.py:180-384, tf:models/vit/modeling_vit.py:
   (autocast's bf16 grad → fp32 .grad);
 * attention via the flash kernels, partial RoPE in place on the fused qkv;
 * cross-entropy fused fwd+bwd over bf16 logits (fp32 math), dlogits in place.
+
+A vision-only classifier (ModelConfig.classifier: ViTForImageClassification,
+tf:models/vit/modeling_vit.py) runs the same ViT encoder, then the final LayerNorm on the CLS
+rows, the classifier GEMM and the cross entropy over one row per image (_cls_forward /
+_cls_backward).
 """
 
 from __future__ import annotations
@@ -120,15 +125,24 @@ class Batch:
     `pos` (int32 [T], the position of each token inside its sequence) carry the geometry to
     the varlen attention and the positional rope; both are None on the dense path (no mask,
     or a mask without zeros), which is then object for object what it was without the
-    argument.  B stays the number of sequences, S the padded width."""
+    argument.  B stays the number of sequences, S the padded width.
 
-    def __init__(self, cfg: ModelConfig, input_ids: torch.Tensor, labels: torch.Tensor,
+    Image batches (a vision-only classifier, ModelConfig.classifier): `input_ids` is None,
+    `pixel_values` is [B, C, S, S] and `labels` [B] holds one class per image, each in
+    [0, num_classes).  num_items = B; S / T count the ViT tokens (patches + CLS)."""
+
+    def __init__(self, cfg: ModelConfig, input_ids: torch.Tensor | None, labels: torch.Tensor,
                  pixel_values: torch.Tensor | None, device: torch.device, stream=None,
                  attention_mask: torch.Tensor | None = None):
         """stream: stage on this (copy) stream instead of the current one — the copies and
         the segment sort then overlap the compute stream's work; `use(stream)` (called by
         Engine.forward) orders the consumer after them."""
         device = torch.device(device)
+        if cfg.classifier:
+            self._init_images(cfg, input_ids, labels, pixel_values, device, stream, attention_mask)
+            return
+        if input_ids is None:
+            raise ValueError("a language model needs input_ids")
         self.B, self.S = input_ids.shape
         if cfg.multimodal and pixel_values is None:
             raise ValueError("multimodal model needs pixel_values")
@@ -144,6 +158,45 @@ class Batch:
             self._ready.record(stream)
         else:
             self._stage(cfg, input_ids, labels, pixel_values, device, mask)
+
+    def _init_images(self, cfg, input_ids, labels, pixel_values, device, stream, attention_mask):
+        v = cfg.vision
+        if input_ids is not None or attention_mask is not None:
+            raise ValueError("an image classifier takes pixel_values and labels, not input_ids / "
+                             "attention_mask")
+        if pixel_values is None:
+            raise ValueError("an image classifier needs pixel_values")
+        want = (v.channels, v.image, v.image)
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != want:
+            raise ValueError(f"pixel_values shape {tuple(pixel_values.shape)} != [B, "
+                             f"{v.channels}, {v.image}, {v.image}]")
+        self.B, self.S = pixel_values.shape[0], v.num_patches + 1
+        if tuple(labels.shape) != (self.B,):
+            raise ValueError(f"labels shape {tuple(labels.shape)} != [{self.B}] (one class per "
+                             "image)")
+        self.T, self.max_len = self.B * self.S, self.S
+        self.lens = [self.S] * self.B
+        self.cu_seqlens = self.pos = None
+        self._ready = None
+        if stream is not None and device.type == "cuda":
+            with torch.cuda.stream(stream):
+                self._stage_images(cfg, labels, pixel_values, device)
+            self._ready = torch.cuda.Event()
+            self._ready.record(stream)
+        else:
+            self._stage_images(cfg, labels, pixel_values, device)
+
+    def _stage_images(self, cfg, labels, pixel_values, device):
+        lab = labels.to(torch.int64)
+        if lab.device.type == "cpu":  # validated on the host copy: no device synchronisation
+            _check_labels(lab.numpy(), cfg.num_classes)
+        elif lab.numel():
+            _check_labels(torch.stack((lab.min(), lab.max())).cpu().numpy(), cfg.num_classes)
+        self.num_items = self.B
+        self.ids = self.img_map = self.loss_rows = self.loss_map = None
+        self.labels = self.loss_labels = _to(lab, device, torch.int64)
+        self.pixels = _to(pixel_values, device, F32)
+        self.segments = ()
 
     def _check_mask(self, attention_mask):
         """None for the dense path (no mask, or no zero in it); else the host bool [B, S] mask,
@@ -331,12 +384,14 @@ class Engine:
         self.s = store
         self.dev = store.device
         t = cfg.text
-        if t.llama:
-            cos, sin = rope_tables_llama3(t.head_dim, t.rope_theta, t.rope_scaling, max_seq)
-        else:
-            cos, sin = rope_tables(t.hidden, t.heads, t.rotary_pct, t.rope_theta, max_seq)
-        self.cos = cos.to(self.dev)
-        self.sin = sin.to(self.dev)
+        self.cos = self.sin = None  # a vision-only classifier has no rope
+        if t is not None:
+            if t.llama:
+                cos, sin = rope_tables_llama3(t.head_dim, t.rope_theta, t.rope_scaling, max_seq)
+            else:
+                cos, sin = rope_tables(t.hidden, t.heads, t.rotary_pct, t.rope_theta, max_seq)
+            self.cos = cos.to(self.dev)
+            self.sin = sin.to(self.dev)
         self.cache: dict = {}
         # activation checkpointing (HF gradient_checkpointing, src/train.py:112 →
         # TrainingClass.gradient_checkpointing): keep only each layer's input residual
@@ -362,13 +417,14 @@ class Engine:
         # gradient in it is final for this micro-batch (DDP overlap, distributed.GradSync)
         self.grad_ready_hook = None
         # every weight whose input gradient is needed gets a transposed bf16 shadow
-        self.head = "text.embed" if t.tie_embeddings else "text.lm_head"
+        tied = t is not None and t.tie_embeddings
+        self.head = "cls_head" if t is None else "text.embed" if tied else "text.lm_head"
         # LLaVA-pretrain freeze (src/models/llava.py:49-52): no weight gradients for the
         # tower / language model, no backward through the tower at all
         self.frozen = cfg.freeze_tower_and_llm
         store.transposed = [n for n in store.shapes if len(store.shapes[n]) == 2 and
                             n not in ("vision.patch.weight", "text.embed", "vision.pos")]
-        if t.tie_embeddings:  # the tied lm_head's input gradient reads E^T
+        if tied:  # the tied lm_head's input gradient reads E^T
             store.transposed.append("text.embed")
         if self.frozen and not t.llama:
             raise NotImplementedError("freeze_tower_and_llm is the llava-pretrain (Llama) recipe")
@@ -381,7 +437,8 @@ class Engine:
         self.dropout_enabled = True
         self.dropout_step = 0
         self.rank = _dp_rank()
-        for layers in (t.layers, cfg.vision.used_layers if cfg.multimodal else 0):
+        for layers in (t.layers if t is not None else 0,
+                       cfg.vision.used_layers if cfg.multimodal else 0):
             if layers >= VISION_UNIT:
                 raise ValueError(f"{layers} layers: dropout_site numbers at most {VISION_UNIT - 1}")
         self._pt = self._pv = 0.0  # the probabilities of the micro-step in flight
@@ -460,6 +517,8 @@ class Engine:
         if cfg.multimodal:
             order += ["vision.patch"] + (["vision.pos"] if "vision.pos" in f32 else [])
             order += [f"vision.layers.{i}" for i in range(cfg.vision.used_layers)]
+            if cfg.classifier:
+                return order + ["cls_head"]
             order += ["proj"]
         order += (["text.embed"] if "text.embed" in f32 else [])
         order += [f"text.layers.{i}" for i in range(cfg.text.layers)]
@@ -623,7 +682,7 @@ class Engine:
         backward and any recompute.  A forward without gradients previews the next step's masks
         and leaves the counter alone."""
         on = self.dropout_enabled
-        self._pt = self.cfg.text.hidden_dropout if on else 0.0
+        self._pt = self.cfg.text.hidden_dropout if on and self.cfg.text is not None else 0.0
         self._pv = self.cfg.vision.hidden_dropout if on and self.cfg.multimodal and \
             not self.frozen else 0.0
         self._dstep = self.dropout_step
@@ -885,7 +944,10 @@ class Engine:
         self._unit_done(f"vision.layers.{i}")
         return dxn, nxt.get("dx_bf16")
 
-    def _vision_fwd(self, pixels, B):
+    def _encoder_fwd(self, pixels, B):
+        """Embeddings + the used encoder layers: the fp32 residual stream [B·(patches+1), h]
+        (what the projector path and the classification head both read), the im2col buffer
+        and the pre-LN's saved tensors for the embedding backward."""
         v = self.cfg.vision
         npch, hv = v.num_patches, v.hidden
         cols = self._e(B * npch, v.patch_k)
@@ -908,6 +970,12 @@ class Engine:
         for i in range(v.used_layers):
             self._unit_fwd(f"vision.layers.{i}")
             h = self._vit_layer_fwd(i, h, B, npch + 1)
+        return h, cols, pre_ln
+
+    def _vision_fwd(self, pixels, B):
+        v = self.cfg.vision
+        npch, hv = v.num_patches, v.hidden
+        h, cols, pre_ln = self._encoder_fwd(pixels, B)
         f = self._e(B * npch, hv)
         K.select_patches_fwd(B, npch, h, f)
         ht = self.cfg.text.hidden
@@ -941,6 +1009,13 @@ class Engine:
         K.cast_f32_bf16(dh, d2)
         if self._pv == 0:  # else the layer sums its masked gradient itself
             K.colsum(d2, self.s.g(f"vision.layers.{top}.fc2.bias"), accumulate=True)
+        self._encoder_bwd(dh, d2, B, cols, pre_ln)
+
+    def _encoder_bwd(self, dh, d2, B, cols, pre_ln):
+        """Backward of _encoder_fwd from the top layer's output gradient: dh fp32, d2 = bf16(dh)
+        (with the top layer's fc2.bias gradient already summed when vision dropout is 0)."""
+        v = self.cfg.vision
+        npch, hv = v.num_patches, v.hidden
         for i in reversed(range(v.used_layers)):
             dh, d2 = self._vit_layer_bwd(i, dh, d2, B, npch + 1)
         if pre_ln is not None:  # through pre_layrnorm (its γ/β grads accumulate)
@@ -959,10 +1034,71 @@ class Engine:
         self._dw(dpo, cols, "vision.patch", bias=v.patch_bias)
         self._unit_done("vision.patch")
 
+    # -------------------------------------------------------------- classification head
+    def _cls_forward(self, batch: Batch, grad_scale: float, need_grad: bool) -> torch.Tensor:
+        """ViTForImageClassification (tf:models/vit/modeling_vit.py): encoder, vit.layernorm on
+        the CLS rows (the only ones the head reads), classifier with its bias, Σ_images CE."""
+        cfg, v = self.cfg, self.cfg.vision
+        B, Sv = batch.B, v.num_patches + 1
+        self._vl = None
+        if self.dev.type == "cuda":
+            batch.use(torch.cuda.current_stream(self.dev))
+        region = getattr(self.units, "region", None)
+        if region is not None:
+            region()
+        self._drop_begin(need_grad)
+        h, cols, pre_ln = self._encoder_fwd(batch.pixels, B)
+        y = self._e(B, v.hidden)
+        m, r = self._e(B, dtype=F32), self._e(B, dtype=F32)
+        K.cls_ln_fwd(h, B, Sv, self.s.p("vision.ln_post.weight"), self.s.p("vision.ln_post.bias"),
+                     v.eps, y, m, r)
+        self._unit_fwd("cls_head")
+        logits = self._linear(y, "cls_head")
+        loss_rows = self._e(B, dtype=F32)
+        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
+                        logits if need_grad else None, vocab_valid=cfg.num_classes)
+        loss = self._e(1, dtype=F32)
+        K.sum_f32(loss_rows, loss)
+        if need_grad:
+            self.cache["head"] = (h, m, r, y, logits)
+            self.cache["vis"] = (cols, pre_ln)
+        else:
+            self.cache.clear()
+        return loss
+
+    def _cls_backward(self, batch: Batch, scale: torch.Tensor | None) -> None:
+        v = self.cfg.vision
+        B, Sv = batch.B, v.num_patches + 1
+        self._vl = None
+        hL, m, r, y, dlogits = self.cache.pop("head")
+        cols, pre_ln = self.cache.pop("vis")
+        if scale is not None:
+            dlogits.mul_(scale.to(torch.float32))
+        self._unit_bwd("cls_head")
+        dy = self._dx(dlogits, "cls_head")
+        self._dw(dlogits, y, "cls_head")  # + the classifier's bias gradient
+        self._unit_done("cls_head")
+        del dlogits
+        # vit.layernorm's backward, the zero rows of the residual-stream gradient and its bf16
+        # copy in one pass; without dropout also the top layer's fc2.bias gradient (the layer
+        # sums its masked gradient itself otherwise)
+        top = f"vision.layers.{v.used_layers - 1}"
+        self._grad_open(top)
+        dh, d2 = self._e(B * Sv, v.hidden, dtype=F32), self._e(B * Sv, v.hidden)
+        K.cls_ln_bwd(hL, B, Sv, m, r, dy, self.s.p("vision.ln_post.weight"), dh, d2,
+                     self.s.g("vision.ln_post.weight"), self.s.g("vision.ln_post.bias"),
+                     dsum=None if self._pv > 0 else self.s.g(top + ".fc2.bias"))
+        self._encoder_bwd(dh, d2, B, cols, pre_ln)
+        self._ready(("vision.", "cls_head."))
+        self._join_side()
+        self.cache.clear()
+
     # -------------------------------------------------------------- whole model
     def forward(self, batch: Batch, grad_scale: float, need_grad: bool = True) -> torch.Tensor:
         """Returns Σ_tokens CE (device fp32 [1]); when need_grad, dlogits are written
         (scaled by grad_scale = 1/num_items of the global batch) and the caches kept."""
+        if self.cfg.classifier:
+            return self._cls_forward(batch, grad_scale, need_grad)
         cfg, t = self.cfg, self.cfg.text
         # S: the longest sequence — the padded width on the dense path, where T = B * S
         B, S, T = batch.B, batch.max_len, batch.T
@@ -1014,6 +1150,8 @@ class Engine:
     def backward(self, batch: Batch, scale: torch.Tensor | None = None) -> None:
         """Accumulates every parameter gradient into the flat grad buffer.  `scale`
         (device scalar, e.g. autograd's grad_output) multiplies the loss gradient."""
+        if self.cfg.classifier:
+            return self._cls_backward(batch, scale)
         cfg, t = self.cfg, self.cfg.text
         B, S, T = batch.B, batch.max_len, batch.T
         self._vl = batch if batch.cu_seqlens is not None else None

@@ -222,6 +222,44 @@ def layernorm_bwd(x, mean, rstd, dy1, w1, dx, dw1, db1, dy2=None, w2=None, dw2=N
               _p(dsum2), ws.data_ptr(), _stream())
 
 
+def cls_ln_fwd(x: torch.Tensor, batch: int, tokens: int, w, b, eps: float, y: torch.Tensor,
+               mean: torch.Tensor, rstd: torch.Tensor) -> None:
+    """K18: y[b] = bf16(LN(x[b*tokens]; w, b)) — the final LayerNorm of a classification head on
+    the CLS row of each sample.  x fp32 dense [batch*tokens, h]; y bf16 [batch, h] (any row
+    stride); mean, rstd fp32 [batch]."""
+    _check(x, torch.float32, "cls_ln.x")
+    _check(y, torch.bfloat16, "cls_ln.y")
+    h = x.shape[1]
+    if tuple(x.shape) != (batch * tokens, h) or not x.is_contiguous():
+        raise ValueError(f"cls_ln_fwd: x must be dense [{batch * tokens}, h]")
+    if tuple(y.shape) != (batch, h) or mean.numel() != batch or rstd.numel() != batch:
+        raise ValueError("cls_ln_fwd: y [batch, h], mean / rstd [batch] expected")
+    _lib.call("mmpt_cls_ln_fwd", batch, tokens, h, float(eps), x.data_ptr(), w.data_ptr(),
+              b.data_ptr(), y.data_ptr(), _ld(y), mean.data_ptr(), rstd.data_ptr(), _stream())
+
+
+def cls_ln_bwd(x, batch: int, tokens: int, mean, rstd, dy, w, dx, dx_bf16=None, dw=None, db=None,
+               dsum=None) -> None:
+    """K18 backward in one pass over dx (fp32 dense [batch*tokens, h]) and, if given, dx_bf16:
+    row b*tokens = LN'(dy[b]; w), every other row +0; dw / db += the LayerNorm's parameter
+    gradients; dsum += bf16(Σ_b bf16(dx[b*tokens])) (needs dx_bf16)."""
+    _check(x, torch.float32, "cls_ln.x")
+    _check(dy, torch.bfloat16, "cls_ln.dy")
+    _check(dx, torch.float32, "cls_ln.dx")
+    h = x.shape[1]
+    for t, name in ((x, "x"), (dx, "dx"), (dx_bf16, "dx_bf16")):
+        if t is not None and (tuple(t.shape) != (batch * tokens, h) or not t.is_contiguous()):
+            raise ValueError(f"cls_ln_bwd: {name} must be dense [{batch * tokens}, {h}]")
+    if dx_bf16 is not None:
+        _check(dx_bf16, torch.bfloat16, "cls_ln.dx_bf16")
+    if tuple(dy.shape) != (batch, h) or mean.numel() != batch or rstd.numel() != batch:
+        raise ValueError("cls_ln_bwd: dy [batch, h], mean / rstd [batch] expected")
+    ws = workspace(_lib.query("mmpt_cls_ln_bwd_workspace_bytes", batch, h), slot=2)
+    _lib.call("mmpt_cls_ln_bwd", batch, tokens, h, x.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+              dy.data_ptr(), _ld(dy), w.data_ptr(), dx.data_ptr(), _p(dx_bf16), _p(dw), _p(db),
+              _p(dsum), ws.data_ptr(), _stream())
+
+
 def layernorm_f32_fwd(x, w, b, eps: float, y, mean, rstd) -> None:
     _check(x, torch.float32, "layernorm_f32.x")
     rows, h = x.shape

@@ -13,8 +13,8 @@ the LLaVA-pretrain recipe (src/models/llava.py:80-124) used for the C3 compositi
 `use_custom_kernels=False` → the plain transformers model built from explicit
     configs (the reference's "naive" branch: eager attention); no fetch.
 `llava-pretrain` is the reference's own CLIP-L/14-336 + Llama-3.2-1B model (with its
-freeze); model types outside the path (roberta, mamba, convnext, vit, llava-finetune,
-vilt-*) raise.
+freeze); `vit` / `vit-bf16` its ViT-L/16 image classifier (src/models/vit.py); model types
+outside the path (roberta, mamba, convnext, llava-finetune, vilt-*) raise.
 """
 
 from __future__ import annotations
@@ -27,7 +27,8 @@ import torch
 import torch.nn as nn
 
 from . import config as C
-from .data import DummyMultimodalLanguageModelingDataset, DummyTextModelingDataset
+from .data import (DummyImageClassificationDataset, DummyMultimodalLanguageModelingDataset,
+                   DummyTextModelingDataset)
 from .engine import Batch, Engine
 from .params import ParamStore, init_normal
 
@@ -35,11 +36,12 @@ PythiaT = Literal["pythia-14m", "pythia-31m", "pythia-70m", "pythia-160m", "pyth
                   "pythia-1b", "pythia-1.4b", "pythia-2.8b", "pythia-6.9b", "pythia-12b"]
 VitPythiaT = Literal["vit-b16-pythia-1b", "clip-l14-336-pythia-2.8b"]
 LlavaT = Literal["llava-pretrain", "llava-pretrain-unfrozen"]
-ModelT = Literal[PythiaT, VitPythiaT, LlavaT]
+ViTT = Literal["vit", "vit-bf16"]
+ModelT = Literal[PythiaT, VitPythiaT, LlavaT, ViTT]
 # reference model types that are not on this path (out of scope;
 # llava-finetune needs a private checkpoint, src/models/llava.py:151)
 OUT_OF_SCOPE = ("roberta", "mamba", "convnext-large-1k", "convnext-large-22k",
-                "convnext-xlarge-22k", "vit", "llava-finetune",
+                "convnext-xlarge-22k", "llava-finetune",
                 "vilt-pretrain", "vilt-finetune", "vilt-original-pretrain",
                 "vilt-original-finetune")
 
@@ -218,6 +220,43 @@ class LlavaPretrainModelClass(VitPythiaModelClass):
     image_token_index = property(lambda self: 128256)
 
 
+class ViTModelClass(BaseModelClass):
+    """The reference's `vit` (src/models/vit.py:9-69): ViTForImageClassification on the
+    ViT-L/16-224 in21k config with 21,841 labels and hidden_dropout_prob 0.1; batch 4096,
+    311,948 steps, fp32 (mixed_precision None), Adam lr 1e-3 β (0.9, 0.999) wd 0.03, linear
+    schedule with 10,000 warmup steps, clip 1.0.
+
+    `vit` restates that recipe verbatim and, like the fp16 Pythias, is a faithful record that
+    TrainingClass.build_trainer refuses: this path has bf16-autocast kernels only.  `vit-bf16`
+    is the same model and recipe under bf16 autocast — the runnable variant beside the
+    reference's name, as `llava-pretrain-unfrozen` is beside `llava-pretrain`."""
+
+    def build_model(self, use_custom_kernels: bool = True) -> nn.Module:
+        if use_custom_kernels:
+            return MMPTForPretraining(self.model_config)
+        return build_hf_model(self.model_config)
+
+    @property
+    def model_config(self) -> C.ModelConfig:
+        return C.get_config("vit-l16-cls")
+
+    batch_size = property(lambda self: 4096)
+    training_steps = property(lambda self: 311948)
+    mixed_precision = property(lambda self: "bf16" if self.model_type == "vit-bf16" else None)
+    optimizer = property(lambda self: torch.optim.Adam)
+    optimizer_kwargs = property(lambda self: {"lr": 1e-3, "betas": (0.9, 0.999),
+                                              "weight_decay": 0.03})
+    scheduler_type = property(lambda self: "linear")
+    scheduler_kwargs = property(lambda self: {"num_warmup_steps": 10000})
+    max_grad_norm = property(lambda self: 1.0)
+    fsdp_layers_to_wrap = property(lambda self: ["ViTLayer"])
+    image_size = property(lambda self: 224)
+    num_classes = property(lambda self: 21841)
+
+    def load_dummy_dataset(self, num_samples: int = 20_000):
+        return DummyImageClassificationDataset(self.image_size, self.num_classes, num_samples)
+
+
 def get_model_class(model_type: str) -> BaseModelClass:
     """src/models/__init__.py:240-296 for the types on the MI355X path."""
     if model_type in PythiaModelClass._LR:
@@ -228,6 +267,8 @@ def get_model_class(model_type: str) -> BaseModelClass:
         return ClipPythiaModelClass(model_type)
     if model_type in ("llava-pretrain", "llava-pretrain-unfrozen"):
         return LlavaPretrainModelClass(model_type)
+    if model_type in ("vit", "vit-bf16"):
+        return ViTModelClass(model_type)
     if model_type in OUT_OF_SCOPE:
         raise NotImplementedError(f"model type {model_type!r} is not on the MI355X hot path "
                                   "(SURVEY.md §8 scope)")
@@ -269,6 +310,8 @@ class MMPTForPretraining(nn.Module):
     model object must provide'): forward(input_ids, pixel_values, attention_mask,
     labels, num_items_in_batch) → output with .loss; `.config.hidden_size` /
     `.config.text_config.hidden_size`; gradient_checkpointing_enable();
+    for a vision-only classifier forward(pixel_values, labels [B]) and `.config.hidden_size` /
+    `.num_labels` / `.image_size`;
     parameters named like the flat store (state_dict keys = ParamStore names).
 
     Gradients live in the store's flat fp32 buffer; every `p.grad` is a view of it.
@@ -307,13 +350,21 @@ class MMPTForPretraining(nn.Module):
         self._grad_views = [self.store.g(n) for n in self.store.names()]
         self._attach_grads()
         t = cfg.text
-        text_cfg = SimpleNamespace(hidden_size=t.hidden, num_hidden_layers=t.layers,
-                                   num_attention_heads=t.heads, intermediate_size=t.ffn,
-                                   vocab_size=t.n_vocab, rotary_pct=t.rotary_pct,
-                                   num_key_value_heads=t.n_kv, model_type=t.arch)
-        self.config = SimpleNamespace(hidden_size=t.hidden, text_config=text_cfg,
-                                      use_cache=False, model_type="mmpt",
-                                      image_token_index=cfg.image_token_id)
+        if cfg.classifier:
+            v = cfg.vision
+            self.config = SimpleNamespace(hidden_size=v.hidden, num_hidden_layers=v.layers,
+                                          num_attention_heads=v.heads, intermediate_size=v.ffn,
+                                          image_size=v.image, patch_size=v.patch,
+                                          num_labels=cfg.num_classes, use_cache=False,
+                                          model_type="mmpt")
+        else:
+            text_cfg = SimpleNamespace(hidden_size=t.hidden, num_hidden_layers=t.layers,
+                                       num_attention_heads=t.heads, intermediate_size=t.ffn,
+                                       vocab_size=t.n_vocab, rotary_pct=t.rotary_pct,
+                                       num_key_value_heads=t.n_kv, model_type=t.arch)
+            self.config = SimpleNamespace(hidden_size=t.hidden, text_config=text_cfg,
+                                          use_cache=False, model_type="mmpt",
+                                          image_token_index=cfg.image_token_id)
         self.gradient_checkpointing = False
         self._shadow_version = self.store.master._version
 
@@ -400,6 +451,16 @@ class MMPTForPretraining(nn.Module):
 def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
     """The reference's use_custom_kernels=False branch: plain transformers modules from
     explicit configs (eager attention), no hub access."""
+    if cfg.classifier:
+        from transformers import ViTConfig, ViTForImageClassification
+
+        v = cfg.vision
+        return ViTForImageClassification(ViTConfig(
+            hidden_size=v.hidden, num_hidden_layers=v.layers, num_attention_heads=v.heads,
+            intermediate_size=v.ffn, image_size=v.image, patch_size=v.patch,
+            num_channels=v.channels, layer_norm_eps=v.eps, hidden_act="gelu", qkv_bias=True,
+            hidden_dropout_prob=v.hidden_dropout, attention_probs_dropout_prob=0.0,
+            num_labels=cfg.num_classes, attn_implementation="eager"))
     from transformers import GPTNeoXConfig, GPTNeoXForCausalLM
 
     t = cfg.text

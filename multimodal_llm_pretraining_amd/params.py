@@ -203,7 +203,8 @@ def init_normal(store: ParamStore, seed: int = 0, std: float = 0.02, cfg=None) -
     generated on the CPU so every rank / the oracle see identical bits."""
     g = torch.Generator().manual_seed(seed)
     for name, shape in store.shapes.items():
-        if name.endswith(("ln1.weight", "ln2.weight", "final_ln.weight", "ln_pre.weight")):
+        if name.endswith(("ln1.weight", "ln2.weight", "final_ln.weight", "ln_pre.weight",
+                          "ln_post.weight")):
             t = torch.ones(shape)
         else:
             t = torch.randn(shape, generator=g) * std
@@ -212,5 +213,7 @@ def init_normal(store: ParamStore, seed: int = 0, std: float = 0.02, cfg=None) -
             t[:, v.channels * v.patch * v.patch:] = 0
         if name in ("text.embed", "text.lm_head") and cfg is not None:
             t[cfg.text.n_vocab:] = 0  # vocabulary padding rows (never read, zero gradient)
+        if name in ("cls_head.weight", "cls_head.bias") and cfg is not None:
+            t[cfg.num_classes:] = 0  # class padding rows (outside the softmax, zero gradient)
         store.load({name: t})
     store.refresh_shadow()

@@ -63,6 +63,13 @@ class ManualTrainer:
         if self.cfg.freeze_tower_and_llm and (mode != "ddp" or step_cfg.offload):
             raise NotImplementedError("freeze_tower_and_llm trains the projector only (6.3 M "
                                       "parameters): data parallel without sharding/offload")
+        if self.cfg.classifier and mode in ("zero2", "zero3"):
+            # ZeRO-2/3 and FSDP partition per unit: a text-less model needs a unit order and a
+            # persistence threshold of its own, which are not built
+            raise NotImplementedError(
+                f"sharding {step_cfg.sharding!r} for the vision-only classifier "
+                f"{C.preset_name(self.cfg) or step_cfg.model!r} is not implemented (data "
+                "parallel and zero_1 are)")
         if mode == "zero3" and self.cfg.text.tie_embeddings:
             raise NotImplementedError("ZeRO-3 with a tied lm_head (Llama) is not implemented")
         # ZeRO-2 and ZeRO-3 share the per-unit partition (zero3.py): ZeRO-2 keeps the bf16
@@ -243,7 +250,7 @@ class ManualTrainer:
         asynchronously and the index bookkeeping is built without a device sync; with
         `stream` the staging runs on that copy stream, overlapped with the step.  A right-padded
         `attention_mask` in the loader's dict drops the pad tokens (Batch)."""
-        return Batch(self.cfg, batch["input_ids"], batch["labels"], batch.get("pixel_values"),
+        return Batch(self.cfg, batch.get("input_ids"), batch["labels"], batch.get("pixel_values"),
                      self.device, stream=stream, attention_mask=batch.get("attention_mask"))
 
     def manual_training_step(self, batch: Batch, num_items_global: int,

@@ -51,6 +51,8 @@ def unit_of(name: str) -> str | None:
         return "vision.patch"
     if name == "text.lm_head":
         return "text.lm_head"
+    if name.startswith("cls_head."):
+        return "cls_head"
     raise KeyError(f"no ZeRO-3 unit for parameter {name!r}")
 
 

@@ -24,6 +24,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
+#include "attn_plan.h"
 #include "common.h"
 
 namespace mmpt {
@@ -76,7 +79,6 @@ __device__ __forceinline__ int seq_row0(const AttnParams& p, int b) {
   if constexpr (VL) return __builtin_amdgcn_readfirstlane(p.cu[b]);
   else return b * p.S;
 }
-constexpr int FUSED_ROT = 64;  // the rotary width the fused epilogues handle (Pythia: D / 4)
 
 // The inverse rotary pairs (d, d + 32) of the d-tiles dt = 0, 1 and dt + 2 of an accumulator
 // tile set x[dt] (C rows = dims 16dt + 4g + i, already scaled) at sequence position pos:
@@ -361,9 +363,6 @@ __device__ __forceinline__ int dst_pos(int L) { return L ^ ((L >> 4) & 3); }
 #endif
 #ifndef MMPT_ATTN_SD
 #define MMPT_ATTN_SD 2  // K fragments one k-step ahead (r03: -1.5..2.5% with VD 3, profiles/r03/attn_fwd_ring)
-#endif
-#ifndef MMPT_ATTN_DQ_STAGE
-#define MMPT_ATTN_DQ_STAGE 0
 #endif
 // dK/dV diagnostics (never shipped): 1 = no ring DMA / waits in the loop, 2 = no softmax
 // (P = raw scores), 3 = no S/dP phase, 4 = no dV/dK phase, 5 = no per-block barrier,
@@ -1664,11 +1663,10 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
     vm_wait_all();
     __syncthreads();
   }
-  // past the item's last barrier: dQ through the buffer the last key block used
+  // past the item's last barrier: dQ goes out straight from the accumulators, 8 B per store
   const int cb = b, cq0 = q0 + wave * 16 * QT;
   const int csl = vsl, cr0 = vr0;
   const long cqcol = (long)h * p.hs;
-  char* ostage = smem + ((nkb - 1 + par) & 1) * 2 * I::BYTES + wave * (16 * QT * I::RB);
   wid = wid_n;
   it = itn;
   if (wid >= 0) {
@@ -1685,32 +1683,6 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
     vcol = nvc;
     if (MMPT_ATTN_EARLYQ) load_q();  // next item's Q / dO / lse / δ under the dQ stores
   }
-#if MMPT_ATTN_DQ_STAGE
-  constexpr int CPR = D / 8, RPI = 64 / CPR, SWM = (CPR < 16 ? CPR : 16) - 1;
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    const int r = qt * 16 + (lane & 15);
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      uint2 u;
-      u.x = (uint32_t)f2bf(dq[qt][dt][0] * p.scale) | ((uint32_t)f2bf(dq[qt][dt][1] * p.scale) << 16);
-      u.y = (uint32_t)f2bf(dq[qt][dt][2] * p.scale) | ((uint32_t)f2bf(dq[qt][dt][3] * p.scale) << 16);
-      const int c = 2 * dt + (g >> 1);
-      stage_w8(ostage + r * I::RB, c ^ (r & SWM), g & 1, r, u);
-    }
-  }
-  {
-    const int rr = lane / CPR, c = lane % CPR;
-#pragma unroll
-    for (int i = 0; i < 16 * QT / RPI; ++i) {
-      const int r = i * RPI + rr;
-      const uint4 v = *(const uint4*)(ostage + r * I::RB + ((c ^ (r & SWM)) << 4));
-      if (cq0 + r < LEN(csl) && chunk_real<D>(c, p.dr))
-        *(uint4*)(p.dqkv + (long)(ROW0(cr0, cb) + cq0 + r) * p.ld + cqcol + c * 8) = v;
-    }
-  }
-#else
-  (void)ostage;
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
     if (cq0 + qt * 16 + (lane & 15) >= LEN(csl)) continue;
@@ -1724,7 +1696,6 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
       *(uint2*)(base + dt * 16 + 4 * g) = u;
     }
   }
-#endif
   if (wid < 0) break;
   if (!MMPT_ATTN_EARLYQ) load_q();
   }  // items
@@ -1894,37 +1865,31 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_ds_kernel(AttnParams p) {
   }
 }
 
+// The switches: on unless the environment variable starts with 0; read once, mmpt_set_switch
+// overrides the slot (the bitwise A/B tests).
+int env_switch(int& slot, const char* name) {
+  if (slot < 0) {
+    const char* e = getenv(name);
+    slot = (e != nullptr && e[0] == '0') ? 0 : 1;
+  }
+  return slot;
+}
 // D = 256 backward through dS tiles (MMPT_ATTN_DS, default on): 0 = the recomputing dQ kernel
 int g_attn_ds = -1;
-int attn_ds_mode() {
-  if (g_attn_ds < 0) {
-    const char* e = getenv("MMPT_ATTN_DS");
-    g_attn_ds = (e != nullptr && e[0] == '0') ? 0 : 1;
-  }
-  return g_attn_ds;
-}
+int attn_ds_mode() { return env_switch(g_attn_ds, "MMPT_ATTN_DS"); }
 // D = 256 dK/dV through D-split wave pairs (MMPT_ATTN_PAIR, default on): 0 = the one-wave-
 // per-SIMD ring kernel
-int g_attn_pair = -1;  // read once; mmpt_set_switch overrides it (the bitwise A/B test)
-int attn_pair_mode() {
-  if (g_attn_pair < 0) {
-    const char* e = getenv("MMPT_ATTN_PAIR");
-    g_attn_pair = (e != nullptr && e[0] == '0') ? 0 : 1;
-  }
-  return g_attn_pair;
-}
+int g_attn_pair = -1;
+int attn_pair_mode() { return env_switch(g_attn_pair, "MMPT_ATTN_PAIR"); }
 // head_dim 80 (Pythia-2.8B) on the D = 128 kernels computing 80 dims (MMPT_ATTN_NATIVE80, default
 // on): 0 = all 128 dims with 80.. zero-filled (the round-3 path; bitwise the same results)
 int g_attn_native80 = -1;
-int attn_native80() {
-  if (g_attn_native80 < 0) {
-    const char* e = getenv("MMPT_ATTN_NATIVE80");
-    g_attn_native80 = (e != nullptr && e[0] == '0') ? 0 : 1;
-  }
-  return g_attn_native80;
-}
-size_t ds_offset(int64_t batch, int64_t seq, int64_t heads) {  // after δ, 256-B aligned
-  return ((size_t)(batch * seq * heads) * sizeof(float) + 255) & ~(size_t)255;
+int attn_native80() { return env_switch(g_attn_native80, "MMPT_ATTN_NATIVE80"); }
+// every entry's plan (attn_plan.h) is taken under these: the one place the switches are read
+AttnPlan plan_for(int64_t batch, int64_t seq, int64_t heads, int64_t head_dim, bool varlen,
+                  int64_t rot_dims = 0, bool tables_aligned = false) {
+  const AttnSwitches sw{attn_ds_mode(), attn_pair_mode(), attn_native80()};
+  return attn_plan(batch, seq, heads, head_dim, varlen, rot_dims, tables_aligned, sw);
 }
 
 // Wave layout per head dim: D = 256 -> 8 waves x 16 query rows (2 waves per SIMD: one
@@ -1939,20 +1904,20 @@ size_t ds_offset(int64_t batch, int64_t seq, int64_t heads) {  // after δ, 256-
 #ifndef MMPT_ATTN_DQ256
 #define MMPT_ATTN_DQ256 81   // D = 256 dQ kernel: waves * 10 + query tiles per wave
 #endif
-template <int D>
 #ifndef MMPT_ATTN_FWD128
 #define MMPT_ATTN_FWD128 1  // D = 128 forward: query tiles per wave (round 5: 1, was 2 — C5's
                            // attention forward 1433 -> 1208 us, profiles/r05/attn128/)
 #endif
-constexpr int qtiles() { return D == 128 ? MMPT_ATTN_FWD128 : D == 256 ? MMPT_ATTN_FWD256 % 10 : 1; }
-template <int D>
-constexpr int qwaves() { return D == 256 ? MMPT_ATTN_FWD256 / 10 : 4; }
-template <int D>
 #ifndef MMPT_ATTN_DQ128
 #define MMPT_ATTN_DQ128 1  // D = 128 (and the 80-dim native path) dQ kernel: query tiles per wave
                           // (round 5: 1, was 2 — C5's attention backward 4795 -> 3676 us,
                           // profiles/r05/attn128/)
 #endif
+template <int D>
+constexpr int qtiles() { return D == 128 ? MMPT_ATTN_FWD128 : D == 256 ? MMPT_ATTN_FWD256 % 10 : 1; }
+template <int D>
+constexpr int qwaves() { return D == 256 ? MMPT_ATTN_FWD256 / 10 : 4; }
+template <int D>
 constexpr int dq_qtiles() { return D == 128 ? MMPT_ATTN_DQ128 : D == 256 ? MMPT_ATTN_DQ256 % 10 : 1; }
 template <int D>
 constexpr int dq_qwaves() { return D == 256 ? MMPT_ATTN_DQ256 / 10 : 4; }
@@ -1964,30 +1929,48 @@ int attn_slots() {
   return slots;
 }
 
-template <int D, int DR = D, bool VL = false>
+// The grid of a persistent launch of KERN over `items` work items: CUs x resident workgroups per
+// CU (1 at D = 256: 128 KiB of LDS), the occupancy asked once per kernel instantiation; D = 64
+// (ViT's short sequences) runs one workgroup per item.
+template <auto KERN, int D>
+dim3 persistent_grid(int threads, long items) {
+  static int occ = -1;
+  if (occ < 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)KERN, threads, 0) !=
+                      hipSuccess || occ < 1))
+    occ = 1;
+  const long slots = D >= 128 ? (long)attn_slots() * occ : 0;
+  return dim3((unsigned)(slots > 0 && items > slots ? slots : items));
+}
+
+// f(std::bool_constant<causal>): the CAUSAL instantiation of a launch
+template <class F>
+auto by_causal(bool causal, F f) {
+  return causal ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// f(D, DR as std::integral_constants): the kernel head dims a plan names
+template <class F>
+int by_head_dim(const AttnPlan& pl, F f) {
+  using std::integral_constant;
+  if (pl.D == 64) return f(integral_constant<int, 64>{}, integral_constant<int, 64>{});
+  if (pl.D == 256) return f(integral_constant<int, 256>{}, integral_constant<int, 256>{});
+  if (pl.DR == 80) return f(integral_constant<int, 128>{}, integral_constant<int, 80>{});
+  return f(integral_constant<int, 128>{}, integral_constant<int, 128>{});  // 96, 112: padded to 128
+}
+
+template <int D, int DR, bool VL>
 int run_fwd(const AttnParams& p, bool causal, hipStream_t s) {
   constexpr int QT = qtiles<D>(), NW = qwaves<D>();
   const long items = (long)((p.S + NW * 16 * QT - 1) / (NW * 16 * QT)) * p.B * p.H;
-  // persistent grid: CUs x resident workgroups per CU (1 at D = 256: 128 KiB of LDS)
-  static int occ[2] = {-1, -1};
-  auto grid_for = [&](const void* kern, int& o) {
-    if (o < 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kern, NW * 64, 0) != hipSuccess ||
-                  o < 1))
-      o = 1;
-    const long slots = D >= 128 ? (long)attn_slots() * o : 0;  // D = 64 (ViT): one per block
-    return dim3((unsigned)(slots > 0 && items > slots ? slots : items));
-  };
-  if (causal)
-    attn_fwd_kernel<D, true, QT, NW, DR, VL>
-        <<<grid_for((const void*)attn_fwd_kernel<D, true, QT, NW, DR, VL>, occ[0]), NW * 64, 0, s>>>(p);
-  else
-    attn_fwd_kernel<D, false, QT, NW, DR, VL>
-        <<<grid_for((const void*)attn_fwd_kernel<D, false, QT, NW, DR, VL>, occ[1]), NW * 64, 0, s>>>(p);
+  by_causal(causal, [&](auto c) {
+    constexpr auto kern = attn_fwd_kernel<D, c(), QT, NW, DR, VL>;
+    kern<<<persistent_grid<kern, D>(NW * 64, items), NW * 64, 0, s>>>(p);
+  });
   return check_launch("attention_fwd");
 }
 
-template <int D, int DR = D, bool VL = false>
-int run_bwd(AttnParams p, bool causal, float* delta, hipStream_t s) {
+template <int D, int DR, bool VL>
+int run_bwd(AttnParams p, const AttnPlan& plan, bool causal, float* delta, hipStream_t s) {
   const long rows = (long)p.B * p.S * p.H;
   constexpr int RPB = 4 * (64 / (D / 8));  // (t, h) rows per 256-thread block
   attn_delta_kernel<D, VL><<<(unsigned)((rows + RPB - 1) / RPB), 256, 0, s>>>(p, delta);
@@ -1998,70 +1981,80 @@ int run_bwd(AttnParams p, bool causal, float* delta, hipStream_t s) {
   // dK/dV: key tiles per wave and waves (D = 256: MMPT_ATTN_DKDV256 = waves·10 + tiles)
   constexpr int KT = D == 256 ? MMPT_ATTN_DKDV256 % 10 : 1;
   constexpr int KNW = D == 256 ? MMPT_ATTN_DKDV256 / 10 : 4;
-  dim3 grid((p.S + KNW * 16 * KT - 1) / (KNW * 16 * KT), p.B * p.Hkv);
+  const dim3 grid((p.S + KNW * 16 * KT - 1) / (KNW * 16 * KT), p.B * p.Hkv);
   const long items = (long)((p.S + NW * 16 * QT - 1) / (NW * 16 * QT)) * p.B * p.H;
-  static int occ[2] = {-1, -1};
-  auto gq = [&](const void* kern, int& o) {
-    if (o < 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kern, NW * 64, 0) != hipSuccess ||
-                  o < 1))
-      o = 1;
-    const long slots = D >= 128 ? (long)attn_slots() * o : 0;
-    return dim3((unsigned)(slots > 0 && items > slots ? slots : items));
-  };
-  // (varlen runs the ring dK/dV + recomputing dQ pair at every head dim: the dS tiles and the
-  // wave-pair kernel index by the dense geometry)
+  // The family is the plan's.  The guard only keeps the other instantiations from naming kernels
+  // they do not have: the dS families exist at D = 256, dense, two key tiles per wave.
   if constexpr (D == 256 && KT == 2 && !VL) {
-   if (attn_ds_mode() && p.ds != nullptr) {
-    // dS tiles: the dK/dV kernel writes them, dQ = scale · dS·K reads them
-    dim3 gq((p.S + 127) / 128, p.B * p.H);
-    if (attn_pair_mode()) {  // D-split wave pairs: 128 keys per workgroup as the ring kernel
-      const long pitems = (long)((p.S + 127) / 128) * p.B * p.Hkv;  // persistent: one per CU
-      const long pslots = attn_slots();
-      dim3 gp((unsigned)(pslots > 0 && pitems > pslots ? pslots : pitems));
-      if (causal) attn_bwd_dkdv_pair_kernel<D, true><<<gp, 512, 0, s>>>(p);
-      else attn_bwd_dkdv_pair_kernel<D, false><<<gp, 512, 0, s>>>(p);
-      rc = check_launch("attention_bwd_dkdv");
-      if (rc) return rc;
-      if (causal) attn_bwd_dq_ds_kernel<D, true><<<gq, 256, 0, s>>>(p);
-      else attn_bwd_dq_ds_kernel<D, false><<<gq, 256, 0, s>>>(p);
+    if (plan.family != RING_RECOMPUTE) {
+      // dS tiles: the dK/dV kernel writes them, dQ = scale · dS·K reads them
+      const dim3 gq((p.S + 127) / 128, p.B * p.H);
+      if (plan.family == PAIR_DS) {  // D-split wave pairs: 128 keys per workgroup as the ring kernel
+        const long pitems = (long)((p.S + 127) / 128) * p.B * p.Hkv;  // persistent: one per CU
+        const long pslots = attn_slots();
+        const dim3 gp((unsigned)(pslots > 0 && pitems > pslots ? pslots : pitems));
+        by_causal(causal, [&](auto c) { attn_bwd_dkdv_pair_kernel<D, c()><<<gp, 512, 0, s>>>(p); });
+        rc = check_launch("attention_bwd_dkdv");
+        if (rc) return rc;
+        by_causal(causal, [&](auto c) { attn_bwd_dq_ds_kernel<D, c()><<<gq, 256, 0, s>>>(p); });
+        return check_launch("attention_bwd");
+      }
+      by_causal(causal, [&](auto c) {
+        attn_bwd_dkdv_ring_kernel<D, c(), KT, KNW, true><<<grid, KNW * 64, 0, s>>>(p);
+        attn_bwd_dq_ds_kernel<D, c()><<<gq, 256, 0, s>>>(p);
+      });
       return check_launch("attention_bwd");
     }
-    if (causal) {
-      attn_bwd_dkdv_ring_kernel<D, true, KT, KNW, true><<<grid, KNW * 64, 0, s>>>(p);
-      attn_bwd_dq_ds_kernel<D, true><<<gq, 256, 0, s>>>(p);
-    } else {
-      attn_bwd_dkdv_ring_kernel<D, false, KT, KNW, true><<<grid, KNW * 64, 0, s>>>(p);
-      attn_bwd_dq_ds_kernel<D, false><<<gq, 256, 0, s>>>(p);
-    }
-    return check_launch("attention_bwd");
-   }
   }
-  if (causal) {
-    attn_bwd_dkdv_ring_kernel<D, true, KT, KNW, false, DR, VL><<<grid, KNW * 64, 0, s>>>(p);
-    attn_bwd_dq_kernel<D, true, QT, NW, DR, VL>
-        <<<gq((const void*)attn_bwd_dq_kernel<D, true, QT, NW, DR, VL>, occ[0]), NW * 64, 0, s>>>(p);
-  } else {
-    attn_bwd_dkdv_ring_kernel<D, false, KT, KNW, false, DR, VL><<<grid, KNW * 64, 0, s>>>(p);
-    attn_bwd_dq_kernel<D, false, QT, NW, DR, VL>
-        <<<gq((const void*)attn_bwd_dq_kernel<D, false, QT, NW, DR, VL>, occ[1]), NW * 64, 0, s>>>(p);
-  }
+  by_causal(causal, [&](auto c) {
+    attn_bwd_dkdv_ring_kernel<D, c(), KT, KNW, false, DR, VL><<<grid, KNW * 64, 0, s>>>(p);
+    constexpr auto dq = attn_bwd_dq_kernel<D, c(), QT, NW, DR, VL>;
+    dq<<<persistent_grid<dq, D>(NW * 64, items), NW * 64, 0, s>>>(p);
+  });
   return check_launch("attention_bwd");
 }
 
-// The varlen entries' own checks, after validate(batch, max_seq, ...): the packed token count
-// takes the place of batch * seq in the 32-bit row-offset limits.
-int validate_varlen(int64_t batch, int64_t max_seq, int64_t total, const void* cu) {
-  MMPT_REQUIRE(cu != nullptr, "attention_varlen: null cu_seqlens");
-  MMPT_REQUIRE(((uintptr_t)cu & 3) == 0, "attention_varlen: cu_seqlens must be 4-B aligned");
-  MMPT_REQUIRE(total >= batch && total <= batch * max_seq,
-               "attention_varlen: total_tokens %lld outside [batch, batch * max_seq] = [%lld, %lld]",
-               (long long)total, (long long)batch, (long long)(batch * max_seq));
-  MMPT_REQUIRE(total < (1LL << 31), "attention_varlen: too many tokens");
-  return MMPT_OK;
+// the kernels a plan names, dense (VL = false) or varlen
+template <bool VL>
+int launch_fwd(const AttnParams& p, const AttnPlan& plan, bool causal, void* stream) {
+  return by_head_dim(plan, [&](auto D, auto DR) {
+    return run_fwd<D(), DR(), VL>(p, causal, (hipStream_t)stream);
+  });
+}
+template <bool VL>
+int launch_bwd(const AttnParams& p, const AttnPlan& plan, bool causal, void* workspace, void* stream) {
+  return by_head_dim(plan, [&](auto D, auto DR) {
+    return run_bwd<D(), DR(), VL>(p, plan, causal, (float*)workspace, (hipStream_t)stream);
+  });
 }
 
-int validate(int64_t batch, int64_t seq, int64_t heads, int64_t head_dim, const void* qkv,
-             int64_t ld, int64_t hs, int64_t ps) {
+// What the varlen entries add to a call (null: dense) ...
+struct AttnVarlen {
+  const int32_t* cu;
+  int64_t total;
+};
+// ... and the backward ones (null: forward).  ps / rot / rcos / rsin: the fused rope backward's
+// part stride and tables, zero on every other path.
+struct AttnBwdOps {
+  const void* dout;
+  void* dqkv;
+  void* workspace;
+  int64_t ps = 0, rot = 0;
+  const float* rcos = nullptr;
+  const float* rsin = nullptr;
+};
+
+// Every entry's argument checks and its AttnParams.  The layout is the GQA form (G = heads /
+// kv_heads query heads per kv head, k / v at their own offsets); seq is max_seq for a varlen
+// call, where the packed token count takes the place of batch * seq in the 32-bit row-offset
+// limits; out / lse are the forward's outputs, or its results as the backward reads them.
+// `entry` names the caller in the texts that are its own.
+int attn_params(AttnParams& p, const AttnPlan& plan, const char* entry, int64_t batch, int64_t seq,
+                int64_t heads, int64_t kv_heads, int64_t head_dim, const void* qkv, int64_t ld,
+                int64_t hs, int64_t k_off, int64_t v_off, float scale, const void* out,
+                int64_t ld_out, const float* lse, const AttnVarlen* vl, const AttnBwdOps* bw) {
+  const int64_t ps = bw ? bw->ps : 0;
+  if (vl) MMPT_REQUIRE(seq >= 1, "attention_varlen: max_seq %lld < 1", (long long)seq);
   MMPT_REQUIRE(batch > 0 && seq > 0 && heads > 0, "attention: empty problem");
   MMPT_REQUIRE(head_dim == 64 || head_dim == 256 || (head_dim % 16 == 0 && head_dim >= 80 &&
                                                       head_dim <= 128),
@@ -2072,20 +2065,51 @@ int validate(int64_t batch, int64_t seq, int64_t heads, int64_t head_dim, const 
                "attention: qkv must be 16-B aligned with strides multiple of 8");
   MMPT_REQUIRE(batch * seq < (1LL << 31), "attention: too many tokens");
   MMPT_REQUIRE(seq * ld * 2 < (1LL << 31), "attention: one sequence must span < 2 GiB (32-bit offsets)");
-  return MMPT_OK;
-}
-
-// GQA geometry (G = heads / kv_heads query heads per kv head, k/v at their own offsets)
-int set_kv(AttnParams& p, int64_t heads, int64_t kv_heads, int64_t k_off, int64_t v_off,
-           int64_t kv_stride) {
+  if (vl) {
+    MMPT_REQUIRE(vl->cu != nullptr, "attention_varlen: null cu_seqlens");
+    MMPT_REQUIRE(((uintptr_t)vl->cu & 3) == 0, "attention_varlen: cu_seqlens must be 4-B aligned");
+    MMPT_REQUIRE(vl->total >= batch && vl->total <= batch * seq,
+                 "attention_varlen: total_tokens %lld outside [batch, batch * max_seq] = [%lld, %lld]",
+                 (long long)vl->total, (long long)batch, (long long)(batch * seq));
+    MMPT_REQUIRE(vl->total < (1LL << 31), "attention_varlen: too many tokens");
+  }
+  if (bw)
+    MMPT_REQUIRE(out && bw->dout && lse && bw->dqkv && bw->workspace && ld_out % 8 == 0,
+                 "%s: null pointer", entry);
+  else
+    MMPT_REQUIRE(out && lse && ld_out % 8 == 0, "%s: bad out/lse", entry);
   MMPT_REQUIRE(kv_heads > 0 && heads % kv_heads == 0, "attention: heads %% kv_heads != 0");
-  MMPT_REQUIRE(k_off % 8 == 0 && v_off % 8 == 0 && kv_stride % 8 == 0 && k_off >= 0 && v_off >= 0,
+  MMPT_REQUIRE(k_off % 8 == 0 && v_off % 8 == 0 && hs % 8 == 0 && k_off >= 0 && v_off >= 0,
                "attention: k/v offsets and stride must be non-negative multiples of 8");
+  p = AttnParams{};
+  p.qkv = (const bf16_t*)qkv;
+  p.ld = ld;
+  p.hs = hs;
+  p.ps = ps;
   p.koff = k_off;
   p.voff = v_off;
-  p.khs = kv_stride;
+  p.khs = hs;
   p.Hkv = (int)kv_heads;
   p.G = (int)(heads / kv_heads);
+  p.B = (int)batch;
+  p.S = (int)seq;
+  p.H = (int)heads;
+  p.scale = scale;
+  p.ld_out = ld_out;
+  p.lse = (float*)lse;
+  p.dr = (int)head_dim;
+  p.cu = vl ? vl->cu : nullptr;
+  if (!bw) {
+    p.out = (bf16_t*)out;
+    return MMPT_OK;
+  }
+  p.o = (const bf16_t*)out;
+  p.dout = (const bf16_t*)bw->dout;
+  p.dqkv = (bf16_t*)bw->dqkv;
+  if (plan.family != RING_RECOMPUTE) p.ds = (bf16_t*)((char*)bw->workspace + plan.ds_offset);
+  p.rcos = bw->rcos;
+  p.rsin = bw->rsin;
+  p.rot = (int)bw->rot;
   return MMPT_OK;
 }
 
@@ -2099,32 +2123,11 @@ extern "C" int mmpt_attention_gqa_fwd(int64_t batch, int64_t seq, int64_t heads,
                                       int64_t head_stride, int64_t k_offset, int64_t v_offset,
                                       int causal, float scale, void* out, int64_t ld_out,
                                       float* lse, void* stream) {
-  int rc = validate(batch, seq, heads, head_dim, qkv, ld, head_stride, 0);
-  if (rc) return rc;
-  MMPT_REQUIRE(out && lse && ld_out % 8 == 0, "attention_fwd: bad out/lse");
-  AttnParams p{};
-  rc = set_kv(p, heads, kv_heads, k_offset, v_offset, head_stride);
-  if (rc) return rc;
-  p.qkv = (const bf16_t*)qkv;
-  p.ld = ld;
-  p.hs = head_stride;
-  p.ps = 0;
-  p.B = (int)batch;
-  p.S = (int)seq;
-  p.H = (int)heads;
-  p.scale = scale;
-  p.out = (bf16_t*)out;
-  p.ld_out = ld_out;
-  p.lse = lse;
-  p.dr = (int)head_dim;
-  hipStream_t s = (hipStream_t)stream;
-  switch (head_dim) {
-    case 64: return run_fwd<64>(p, causal, s);
-    case 256: return run_fwd<256>(p, causal, s);
-    case 80: if (attn_native80()) return run_fwd<128, 80>(p, causal, s);
-      return run_fwd<128>(p, causal, s);
-    default: return run_fwd<128>(p, causal, s);  // 96, 112: padded to 128
-  }
+  const AttnPlan plan = plan_for(batch, seq, heads, head_dim, false);
+  AttnParams p;
+  const int rc = attn_params(p, plan, "attention_fwd", batch, seq, heads, kv_heads, head_dim, qkv, ld,
+                             head_stride, k_offset, v_offset, scale, out, ld_out, lse, nullptr, nullptr);
+  return rc ? rc : launch_fwd<false>(p, plan, causal, stream);
 }
 
 extern "C" int mmpt_attention_varlen_fwd(int64_t batch, int64_t max_seq, int64_t total_tokens,
@@ -2133,43 +2136,19 @@ extern "C" int mmpt_attention_varlen_fwd(int64_t batch, int64_t max_seq, int64_t
                                          int64_t k_offset, int64_t v_offset, int causal,
                                          float scale, const int32_t* cu_seqlens, void* out,
                                          int64_t ld_out, float* lse, void* stream) {
-  MMPT_REQUIRE(max_seq >= 1, "attention_varlen: max_seq %lld < 1", (long long)max_seq);
-  int rc = validate(batch, max_seq, heads, head_dim, qkv, ld, head_stride, 0);
-  if (rc) return rc;
-  rc = validate_varlen(batch, max_seq, total_tokens, cu_seqlens);
-  if (rc) return rc;
-  MMPT_REQUIRE(out && lse && ld_out % 8 == 0, "attention_varlen_fwd: bad out/lse");
-  AttnParams p{};
-  rc = set_kv(p, heads, kv_heads, k_offset, v_offset, head_stride);
-  if (rc) return rc;
-  p.qkv = (const bf16_t*)qkv;
-  p.ld = ld;
-  p.hs = head_stride;
-  p.ps = 0;
-  p.B = (int)batch;
-  p.S = (int)max_seq;
-  p.H = (int)heads;
-  p.scale = scale;
-  p.out = (bf16_t*)out;
-  p.ld_out = ld_out;
-  p.lse = lse;
-  p.dr = (int)head_dim;
-  p.cu = cu_seqlens;
-  hipStream_t s = (hipStream_t)stream;
-  switch (head_dim) {
-    case 64: return run_fwd<64, 64, true>(p, causal, s);
-    case 256: return run_fwd<256, 256, true>(p, causal, s);
-    case 80: if (attn_native80()) return run_fwd<128, 80, true>(p, causal, s);
-      return run_fwd<128, 128, true>(p, causal, s);
-    default: return run_fwd<128, 128, true>(p, causal, s);  // 96, 112: padded to 128
-  }
+  const AttnPlan plan = plan_for(batch, max_seq, heads, head_dim, true);
+  const AttnVarlen vl{cu_seqlens, total_tokens};
+  AttnParams p;
+  const int rc = attn_params(p, plan, "attention_varlen_fwd", batch, max_seq, heads, kv_heads, head_dim,
+                             qkv, ld, head_stride, k_offset, v_offset, scale, out, ld_out, lse, &vl,
+                             nullptr);
+  return rc ? rc : launch_fwd<true>(p, plan, causal, stream);
 }
 
 // δ only: the varlen backward takes the ring dK/dV + recomputing dQ kernels at every head dim
 extern "C" int64_t mmpt_attention_varlen_bwd_workspace_bytes(int64_t batch, int64_t max_seq,
                                                              int64_t heads, int64_t head_dim) {
-  (void)head_dim;
-  return batch * max_seq * heads * (int64_t)sizeof(float);
+  return plan_for(batch, max_seq, heads, head_dim, true).workspace_bytes;
 }
 
 extern "C" int mmpt_attention_varlen_bwd(int64_t batch, int64_t max_seq, int64_t total_tokens,
@@ -2179,49 +2158,20 @@ extern "C" int mmpt_attention_varlen_bwd(int64_t batch, int64_t max_seq, int64_t
                                          float scale, const int32_t* cu_seqlens, const void* out,
                                          const void* dout, int64_t ld_out, const float* lse,
                                          void* dqkv, void* workspace, void* stream) {
-  MMPT_REQUIRE(max_seq >= 1, "attention_varlen: max_seq %lld < 1", (long long)max_seq);
-  int rc = validate(batch, max_seq, heads, head_dim, qkv, ld, head_stride, 0);
-  if (rc) return rc;
-  rc = validate_varlen(batch, max_seq, total_tokens, cu_seqlens);
-  if (rc) return rc;
-  MMPT_REQUIRE(out && dout && lse && dqkv && workspace && ld_out % 8 == 0,
-               "attention_varlen_bwd: null pointer");
-  AttnParams p{};
-  rc = set_kv(p, heads, kv_heads, k_offset, v_offset, head_stride);
-  if (rc) return rc;
-  p.qkv = (const bf16_t*)qkv;
-  p.ld = ld;
-  p.hs = head_stride;
-  p.ps = 0;
-  p.B = (int)batch;
-  p.S = (int)max_seq;
-  p.H = (int)heads;
-  p.scale = scale;
-  p.ld_out = ld_out;
-  p.lse = (float*)lse;
-  p.o = (const bf16_t*)out;
-  p.dout = (const bf16_t*)dout;
-  p.dqkv = (bf16_t*)dqkv;
-  p.dr = (int)head_dim;
-  p.ds = nullptr;
-  p.cu = cu_seqlens;
-  hipStream_t s = (hipStream_t)stream;
-  switch (head_dim) {
-    case 64: return run_bwd<64, 64, true>(p, causal, (float*)workspace, s);
-    case 256: return run_bwd<256, 256, true>(p, causal, (float*)workspace, s);
-    case 80: if (attn_native80()) return run_bwd<128, 80, true>(p, causal, (float*)workspace, s);
-      return run_bwd<128, 128, true>(p, causal, (float*)workspace, s);
-    default: return run_bwd<128, 128, true>(p, causal, (float*)workspace, s);  // 96, 112: padded
-  }
+  const AttnPlan plan = plan_for(batch, max_seq, heads, head_dim, true);
+  const AttnVarlen vl{cu_seqlens, total_tokens};
+  const AttnBwdOps bw{dout, dqkv, workspace};
+  AttnParams p;
+  const int rc = attn_params(p, plan, "attention_varlen_bwd", batch, max_seq, heads, kv_heads, head_dim,
+                             qkv, ld, head_stride, k_offset, v_offset, scale, out, ld_out, lse, &vl, &bw);
+  return rc ? rc : launch_bwd<true>(p, plan, causal, workspace, stream);
 }
 
+// δ (fp32 per query row), then at D = 256 the dS tiles: ceil(S/32)^2 tiles of 2 KiB per
+// (batch, head)
 extern "C" int64_t mmpt_attention_bwd_workspace_bytes(int64_t batch, int64_t seq, int64_t heads,
                                                       int64_t head_dim) {
-  // δ (fp32 per query row), then at D = 256 the dS tiles: ceil(S/32)^2 tiles of 2 KiB per
-  // (batch, head)
-  if (head_dim != 256 || !attn_ds_mode()) return batch * seq * heads * (int64_t)sizeof(float);
-  const int64_t nq = (seq + 31) / 32;
-  return (int64_t)ds_offset(batch, seq, heads) + batch * heads * nq * nq * 2048;
+  return plan_for(batch, seq, heads, head_dim, false).workspace_bytes;
 }
 
 extern "C" int mmpt_attention_gqa_bwd(int64_t batch, int64_t seq, int64_t heads, int64_t kv_heads,
@@ -2230,47 +2180,18 @@ extern "C" int mmpt_attention_gqa_bwd(int64_t batch, int64_t seq, int64_t heads,
                                       int causal, float scale, const void* out, const void* dout,
                                       int64_t ld_out, const float* lse, void* dqkv,
                                       void* workspace, void* stream) {
-  int rc = validate(batch, seq, heads, head_dim, qkv, ld, head_stride, 0);
-  if (rc) return rc;
-  MMPT_REQUIRE(out && dout && lse && dqkv && workspace && ld_out % 8 == 0,
-               "attention_bwd: null pointer");
-  AttnParams p{};
-  rc = set_kv(p, heads, kv_heads, k_offset, v_offset, head_stride);
-  if (rc) return rc;
-  p.qkv = (const bf16_t*)qkv;
-  p.ld = ld;
-  p.hs = head_stride;
-  p.ps = 0;
-  p.B = (int)batch;
-  p.S = (int)seq;
-  p.H = (int)heads;
-  p.scale = scale;
-  p.ld_out = ld_out;
-  p.lse = (float*)lse;
-  p.o = (const bf16_t*)out;
-  p.dout = (const bf16_t*)dout;
-  p.dqkv = (bf16_t*)dqkv;
-  p.dr = (int)head_dim;
-  p.ds = head_dim == 256 && attn_ds_mode()
-             ? (bf16_t*)((char*)workspace + ds_offset(batch, seq, heads)) : nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  switch (head_dim) {
-    case 64: return run_bwd<64>(p, causal, (float*)workspace, s);
-    case 256: return run_bwd<256>(p, causal, (float*)workspace, s);
-    case 80: if (attn_native80()) return run_bwd<128, 80>(p, causal, (float*)workspace, s);
-      return run_bwd<128>(p, causal, (float*)workspace, s);
-    default: return run_bwd<128>(p, causal, (float*)workspace, s);  // 96, 112: padded
-  }
+  const AttnPlan plan = plan_for(batch, seq, heads, head_dim, false);
+  const AttnBwdOps bw{dout, dqkv, workspace};
+  AttnParams p;
+  const int rc = attn_params(p, plan, "attention_bwd", batch, seq, heads, kv_heads, head_dim, qkv, ld,
+                             head_stride, k_offset, v_offset, scale, out, ld_out, lse, nullptr, &bw);
+  return rc ? rc : launch_bwd<false>(p, plan, causal, workspace, stream);
 }
 
 // mmpt_attention_bwd followed by the rope backward of the q and k parts (mmpt_rope_inplace,
 // inverse, parts = 2) — GPTNeoX's `apply_rotary_pos_emb` backward.  On the D = 256 wave-pair +
 // dS-tile path with 64 rotary dims the dK / dQ epilogues rotate before they store (no second
 // pass over dQKV); otherwise the rope kernel runs after the attention backward.
-extern "C" int mmpt_rope_inplace(int64_t tokens, int64_t seq, int64_t heads, int64_t head_dim,
-                                 int64_t rot_dims, void* qkv, int64_t ld, int64_t head_stride,
-                                 int64_t part_stride, int64_t parts, const float* cos,
-                                 const float* sin, int inverse, void* stream);
 extern "C" int mmpt_attention_bwd_rope(int64_t batch, int64_t seq, int64_t heads, int64_t head_dim,
                                        const void* qkv, int64_t ld, int64_t head_stride,
                                        int64_t part_stride, int causal, float scale, const void* out,
@@ -2279,9 +2200,9 @@ extern "C" int mmpt_attention_bwd_rope(int64_t batch, int64_t seq, int64_t heads
                                        const float* cos, const float* sin, void* stream) {
   MMPT_REQUIRE(rot_dims > 0 && rot_dims % 2 == 0 && rot_dims <= head_dim && cos && sin,
                "attention_bwd_rope: bad rotary tables");
-  const bool fused = head_dim == 256 && rot_dims == FUSED_ROT && attn_ds_mode() &&
-                     attn_pair_mode() && ((uintptr_t)cos & 15) == 0 && ((uintptr_t)sin & 15) == 0;
-  if (!fused) {
+  const bool aligned = ((uintptr_t)cos & 15) == 0 && ((uintptr_t)sin & 15) == 0;
+  const AttnPlan plan = plan_for(batch, seq, heads, head_dim, false, rot_dims, aligned);
+  if (!plan.fused_rope) {
     int rc = mmpt_attention_gqa_bwd(batch, seq, heads, heads, head_dim, qkv, ld, head_stride,
                                     part_stride, 2 * part_stride, causal, scale, out, dout, ld_out,
                                     lse, dqkv, workspace, stream);
@@ -2289,32 +2210,12 @@ extern "C" int mmpt_attention_bwd_rope(int64_t batch, int64_t seq, int64_t heads
     return mmpt_rope_inplace(batch * seq, seq, heads, head_dim, rot_dims, dqkv, ld, head_stride,
                              part_stride, 2, cos, sin, 1, stream);
   }
-  int rc = validate(batch, seq, heads, head_dim, qkv, ld, head_stride, part_stride);
-  if (rc) return rc;
-  MMPT_REQUIRE(out && dout && lse && dqkv && workspace && ld_out % 8 == 0,
-               "attention_bwd_rope: null pointer");
-  AttnParams p{};
-  rc = set_kv(p, heads, heads, part_stride, 2 * part_stride, head_stride);
-  if (rc) return rc;
-  p.qkv = (const bf16_t*)qkv;
-  p.ld = ld;
-  p.hs = head_stride;
-  p.ps = part_stride;
-  p.B = (int)batch;
-  p.S = (int)seq;
-  p.H = (int)heads;
-  p.scale = scale;
-  p.ld_out = ld_out;
-  p.lse = (float*)lse;
-  p.o = (const bf16_t*)out;
-  p.dout = (const bf16_t*)dout;
-  p.dqkv = (bf16_t*)dqkv;
-  p.dr = (int)head_dim;
-  p.ds = (bf16_t*)((char*)workspace + ds_offset(batch, seq, heads));
-  p.rcos = cos;
-  p.rsin = sin;
-  p.rot = (int)rot_dims;
-  return run_bwd<256>(p, causal, (float*)workspace, (hipStream_t)stream);
+  const AttnBwdOps bw{dout, dqkv, workspace, part_stride, rot_dims, cos, sin};
+  AttnParams p;
+  const int rc = attn_params(p, plan, "attention_bwd_rope", batch, seq, heads, heads, head_dim, qkv, ld,
+                             head_stride, part_stride, 2 * part_stride, scale, out, ld_out, lse,
+                             nullptr, &bw);
+  return rc ? rc : launch_bwd<false>(p, plan, causal, workspace, stream);
 }
 
 // The fused-qkv layouts of GPTNeoX (per-head interleaved q|k|v) and ViT/CLIP (planar) as

@@ -463,6 +463,58 @@ int mmpt_dropout_mask(int64_t n, double p, uint64_t seed, uint64_t site, uint8_t
                       void* stream);
 
 /* ------------------------------------------------------------------------
+ * K19  attention-probability dropout: nn.Dropout on the softmax output (GPTNeoX / Llama / CLIP
+ * `attention_dropout`, ViT `attention_probs_dropout_prob`; SDPA's dropout_p) inside the
+ * flash-attention kernels.  The masks are never stored.  The keep bit is a pure function of
+ * (seed, site, batch index b, QUERY head h, query position q, key position k) — positions inside
+ * their sequence, b the index in cu_seqlens for a packed call — and of nothing else: not the
+ * kernel, tile shape or head dim, not dense vs varlen, not the GQA grouping.  One Philox4x32-10
+ * call covers a block of 4 queries x 4 keys:
+ *   W    = philox4x32_10(ctr = {(q>>2) | ((k>>2) << 16), b*heads + h, lo32(site), hi32(site)},
+ *                        key = {lo32(seed), hi32(seed)})
+ *   byte = (W.w[q & 3] >> (8 * (k & 3))) & 0xFF
+ *   keep iff byte >= t8,  t8 = floor(p * 256)  (host arithmetic in double)
+ * p is thereby quantised: p_eff = t8 / 256 (mmpt_attn_dropout_p_eff), and kept probabilities are
+ * multiplied by s = float(1 / (1 - p_eff)).  t8 == 0 (p < 1/256) is the p = 0 path: the drop
+ * entries then run the kernels and write the bits of the plain entries.  A site must be one that
+ * no hidden-dropout (K16) call of the same seed uses: both share the Philox key.
+ * Arithmetic and rounding order (P = the undropped softmax, lse its log-sum-exp, unchanged):
+ *   forward   O = bf16(acc * ((1 / l) * s)), acc = Σ_k bf16(keep ? P~ : 0) · V in fp32, P~ and the
+ *             row sum l as in the plain kernel (the dropped P is zeroed before the bf16 pack, s is
+ *             folded into the fp32 epilogue);
+ *   dV        = bf16(s * Σ_q bf16(keep ? P : 0) · dO)  (s in the fp32 epilogue);
+ *   dS        = bf16(P * ((keep ? dP * s : 0) - δ)) with dP, δ = rowsum(dO∘O) in fp32; dQ and dK
+ *             from dS as in the plain kernels.
+ * 0 <= p < 1 else MMPT_ERR_ARG; p >= 1/256 with max_seq > 262144 is MMPT_ERR_UNSUPPORTED (the
+ * block indices are 16 bits each).  Added without a change of MMPT_ABI_VERSION: the entries are
+ * new, nothing existing changed.
+ * ---------------------------------------------------------------------- */
+/* Arguments of mmpt_attention_varlen_fwd / _bwd, then p, seed, site.  cu_seqlens == NULL is the
+ * dense call: max_seq is seq and total_tokens must be batch * seq (lse [batch][heads][seq]).
+ * Every head dim of the dense path, causal or not, GQA.  With dropout on the backward runs the
+ * ring dK/dV and recomputing dQ kernels at every head dim (head_dim 256 too) and fuses no rope
+ * backward: run mmpt_rope_inplace(_pos) on dqkv afterwards. */
+int mmpt_attention_drop_fwd(int64_t batch, int64_t max_seq, int64_t total_tokens, int64_t heads,
+                            int64_t kv_heads, int64_t head_dim, const void* qkv, int64_t ld,
+                            int64_t head_stride, int64_t k_offset, int64_t v_offset, int causal,
+                            float scale, const int32_t* cu_seqlens, void* out, int64_t ld_out,
+                            float* lse, double p, uint64_t seed, uint64_t site, void* stream);
+/* δ only when dropout is on (t8 > 0); else what the plain dense (varlen = 0) or varlen entry
+ * asks for. */
+int64_t mmpt_attention_drop_bwd_workspace_bytes(int64_t batch, int64_t max_seq, int64_t heads,
+                                                int64_t head_dim, int varlen, double p);
+int mmpt_attention_drop_bwd(int64_t batch, int64_t max_seq, int64_t total_tokens, int64_t heads,
+                            int64_t kv_heads, int64_t head_dim, const void* qkv, int64_t ld,
+                            int64_t head_stride, int64_t k_offset, int64_t v_offset, int causal,
+                            float scale, const int32_t* cu_seqlens, const void* out,
+                            const void* dout, int64_t ld_out, const float* lse, void* dqkv,
+                            void* workspace, double p, uint64_t seed, uint64_t site, void* stream);
+/* Test / diagnostic hook: keep [batch][heads][seq_q][seq_k] = 1 or 0. */
+int mmpt_attn_dropout_mask(int64_t batch, int64_t heads, int64_t seq_q, int64_t seq_k, double p,
+                           uint64_t seed, uint64_t site, uint8_t* keep, void* stream);
+double mmpt_attn_dropout_p_eff(double p);
+
+/* ------------------------------------------------------------------------
  * K18  classification head: ViTForImageClassification (tf:models/vit/modeling_vit.py,
  * ViTModel(add_pooling_layer=False).layernorm then `classifier(sequence_output[:, 0, :])`).
  * HF runs vit.layernorm (fp32 under autocast) over every token and reads only the CLS row; these

@@ -98,6 +98,11 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_dropout_f32": (I32, [I64, I64, P, P, F64, U64, U64, P]),
     "mmpt_dropout_add_f32": (I32, [I64, I64, P, I64, U64, P, I64, U64, P, P, F64, U64, P]),
     "mmpt_dropout_mask": (I32, [I64, F64, U64, U64, P, P]),
+    "mmpt_attention_drop_fwd": (I32, [I64, I64, I64, I64, I64, I64, P, I64, I64, I64, I64, I32, F32, P, P, I64, P, F64, U64, U64, P]),
+    "mmpt_attention_drop_bwd_workspace_bytes": (I64, [I64, I64, I64, I64, I32, F64]),
+    "mmpt_attention_drop_bwd": (I32, [I64, I64, I64, I64, I64, I64, P, I64, I64, I64, I64, I32, F32, P, P, P, I64, P, P, P, F64, U64, U64, P]),
+    "mmpt_attn_dropout_mask": (I32, [I64, I64, I64, I64, F64, U64, U64, P, P]),
+    "mmpt_attn_dropout_p_eff": (F64, [F64]),
     "mmpt_cls_ln_fwd": (I32, [I64, I64, I64, F32, P, P, P, P, I64, P, P, P]),
     "mmpt_cls_ln_bwd_workspace_bytes": (I64, [I64, I64]),
     "mmpt_cls_ln_bwd": (I32, [I64, I64, I64, P, P, P, P, I64, P, P, P, P, P, P, P, P]),

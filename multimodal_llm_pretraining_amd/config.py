@@ -11,9 +11,9 @@ from __future__ import annotations
 from dataclasses import dataclass, replace
 
 
-def _check_dropout(p: float, where: str) -> None:
+def _check_dropout(p: float, where: str, field: str = "hidden_dropout") -> None:
     if not 0.0 <= p < 1.0:
-        raise ValueError(f"{where}.hidden_dropout must lie in [0, 1), got {p!r}")
+        raise ValueError(f"{where}.{field} must lie in [0, 1), got {p!r}")
 
 
 @dataclass(frozen=True)
@@ -38,9 +38,14 @@ class VisionConfig:
     # ViTConfig.hidden_dropout_prob: ViTEmbeddings.dropout, ViTSelfOutput.dropout and
     # ViTOutput.dropout in training mode.  The ViT tower only: CLIP has no hidden dropout
     hidden_dropout: float = 0.0
+    # ViTConfig.attention_probs_dropout_prob / CLIPVisionConfig.attention_dropout: dropout on the
+    # softmax output in training mode, inside the flash-attention kernels (include/mmpt.h K19;
+    # the probability is quantised to floor(p * 256) / 256)
+    attention_dropout: float = 0.0
 
     def __post_init__(self):
         _check_dropout(self.hidden_dropout, "VisionConfig")
+        _check_dropout(self.attention_dropout, "VisionConfig", "attention_dropout")
         if self.hidden_dropout > 0 and self.pre_ln:
             raise ValueError("hidden_dropout > 0 on a CLIP tower (pre_ln): CLIPVisionConfig has "
                              "no hidden dropout")
@@ -89,9 +94,16 @@ class TextConfig:
     # GPTNeoXConfig.hidden_dropout: emb_dropout, post_attention_dropout and post_mlp_dropout in
     # training mode.  GPTNeoX only: LlamaConfig has no hidden dropout
     hidden_dropout: float = 0.0
+    # GPTNeoXConfig.attention_dropout / LlamaConfig.attention_dropout: dropout on the softmax
+    # output in training mode, inside the flash-attention kernels (include/mmpt.h K19; the
+    # probability is quantised to floor(p * 256) / 256).  Named attn_dropout here, not
+    # attention_dropout as on VisionConfig: tests/test_dropout_cpu.py pins that a TextConfig has
+    # no attribute of that name
+    attn_dropout: float = 0.0
 
     def __post_init__(self):
         _check_dropout(self.hidden_dropout, "TextConfig")
+        _check_dropout(self.attn_dropout, "TextConfig", "attn_dropout (attention_dropout)")
         if self.hidden_dropout > 0 and self.arch == "llama":
             raise ValueError("hidden_dropout > 0 on a Llama text model: LlamaConfig has no "
                              "hidden dropout")
@@ -259,21 +271,39 @@ PRESETS["tiny-llava-frozen"] = ModelConfig(text=PRESETS["tiny-llava"].text,
                                            image_token_id=1024, freeze_tower_and_llm=True)
 
 
-def with_dropout(cfg: ModelConfig, text: float = 0.0, vision: float = 0.0) -> ModelConfig:
-    """`cfg` with the hidden-dropout probabilities set: `text` on a GPTNeoX language model,
-    `vision` on a ViT tower.  A value > 0 where HF has no hidden dropout (Llama, a CLIP tower) or
-    on a tower the model does not have raises ValueError.  Attention-probability dropout is not
-    modelled."""
+def with_dropout(cfg: ModelConfig, text: float = 0.0, vision: float = 0.0, *,
+                 text_attention: float = 0.0, vision_attention: float = 0.0) -> ModelConfig:
+    """`cfg` with the dropout probabilities set.  Hidden dropout: `text` on a GPTNeoX language
+    model, `vision` on a ViT tower; a value > 0 where HF has no hidden dropout (Llama, a CLIP
+    tower) raises ValueError.  Attention-probability dropout: `text_attention` on the language
+    model (GPTNeoX or Llama; TextConfig.attn_dropout), `vision_attention` on the tower (ViT or
+    CLIP; VisionConfig.attention_dropout).  Any value > 0 on a
+    side the model does not have raises ValueError."""
     if cfg.vision is None:
         if vision > 0:
             raise ValueError("vision hidden_dropout > 0 on a model without a vision tower")
-        return replace(cfg, text=replace(cfg.text, hidden_dropout=text))
+        if vision_attention > 0:
+            raise ValueError("vision attention_dropout > 0 on a model without a vision tower")
+        return replace(cfg, text=replace(cfg.text, hidden_dropout=text,
+                                         attn_dropout=text_attention))
     if cfg.text is None:
         if text > 0:
             raise ValueError("text hidden_dropout > 0 on a model without a text model")
-        return replace(cfg, vision=replace(cfg.vision, hidden_dropout=vision))
-    return replace(cfg, text=replace(cfg.text, hidden_dropout=text),
-                   vision=replace(cfg.vision, hidden_dropout=vision))
+        if text_attention > 0:
+            raise ValueError("text attention_dropout > 0 on a model without a text model")
+        return replace(cfg, vision=replace(cfg.vision, hidden_dropout=vision,
+                                           attention_dropout=vision_attention))
+    return replace(cfg, text=replace(cfg.text, hidden_dropout=text, attn_dropout=text_attention),
+                   vision=replace(cfg.vision, hidden_dropout=vision,
+                                  attention_dropout=vision_attention))
+
+
+# attention-probability dropout 0.1 (tiny-mm-adrop: hidden and attention dropout on both sides)
+PRESETS["tiny-lm-adrop"] = with_dropout(PRESETS["tiny-lm"], text_attention=0.1)
+PRESETS["tiny-mm-adrop"] = with_dropout(PRESETS["tiny-mm"], 0.1, 0.1, text_attention=0.1,
+                                        vision_attention=0.1)
+PRESETS["tiny-llama-adrop"] = with_dropout(PRESETS["tiny-llama"], text_attention=0.1)
+PRESETS["tiny-vit-cls-adrop"] = with_dropout(PRESETS["tiny-vit-cls"], vision_attention=0.1)
 
 
 def get_config(name: str) -> ModelConfig:

@@ -28,6 +28,7 @@
 
 #include "attn_plan.h"
 #include "common.h"
+#include "philox.h"
 
 namespace mmpt {
 namespace {
@@ -63,7 +64,29 @@ struct AttnParams {
   // [cu[b], cu[b+1]) of qkv / out / dout / dqkv; S is then max_seq — the stride of lse / δ and
   // the width the work items are enumerated over.  Null on every dense entry point.
   const int* cu;
+  // attention-probability dropout (mmpt_attention_drop_*, the DROP kernel variants; include/mmpt.h
+  // "K19"): keep iff the element's Philox byte >= dt8; dscale = 1 / (1 - dt8 / 256)
+  uint64_t dseed, dsite;
+  uint32_t dt8;
+  float dscale;
 };
+
+// Attention dropout: the keep bytes of one 4 x 4 block (4 queries x 4 keys, philox.h) of
+// batch-head bh.  A lane of the forward / dQ kernels holds the keys 4kb .. 4kb + 3 of ONE query
+// (word q & 3, byte i = key), a lane of the dK/dV kernel the queries 4qb .. 4qb + 3 of ONE key
+// (byte k & 3 of word i = query): either way one call serves the lane's 4 elements.
+__device__ __forceinline__ philox4 drop_block(const AttnParams& p, int qb, int kb, int bh) {
+  return attn_dropout_words((uint32_t)qb, (uint32_t)kb, (uint32_t)bh, p.dsite, p.dseed);
+}
+// word (lane-dependent index w in 0..3) of a block without a private-memory index
+__device__ __forceinline__ uint32_t drop_word(const philox4& W, int w) {
+  const uint32_t lo = (w & 1) ? W.w[1] : W.w[0], hi = (w & 1) ? W.w[3] : W.w[2];
+  return (w & 2) ? hi : lo;
+}
+// byte-wise keep mask of 4 elements in a row word (forward / dQ): bit 8i set iff byte i >= t8
+__device__ __forceinline__ bool drop_keep(uint32_t word, int i, uint32_t t8) {
+  return ((word >> (8 * i)) & 0xFFu) >= t8;
+}
 
 // Row geometry of sequence b (wave-uniform b): its length and its first row.  Dense (VL =
 // false): S and b·S, the expressions the dense kernels always used.  VL: from cu, pinned to
@@ -395,7 +418,7 @@ __device__ __forceinline__ int dst_pos(int L) { return L ^ ((L >> 4) & 3); }
 // One workgroup = 4 waves = 64·QT query rows; wave w owns QT 16-row query tiles.
 // K/V blocks of 64 keys are double-buffered in LDS by LDS-DMA (128 KiB at D=256):
 // the DMA of block j+1 is issued before the MFMAs of block j.
-template <int D, bool CAUSAL, int QT, int NW, int DR = D, bool VL = false>
+template <int D, bool CAUSAL, int QT, int NW, int DR = D, bool VL = false, bool DROP = false>
 __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
   using I = Img<D>;
   constexpr int KS = dr_ksteps<D, DR>(), DT = DR / 16;
@@ -555,6 +578,9 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
     for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) s[qt][kt] = v4f{0.f, 0.f, 0.f, 0.f};
+    // DROP: the keep bytes of (query myq[qt], keys k0 + 16kt + 4g + i), byte i; a tile wholly
+    // above the diagonal draws nothing (its P is 0 whatever the bytes)
+    uint32_t dkeep[DROP ? QT : 1][4] = {};
     // K fragments software-pipelined SD k-steps ahead in registers (hipcc's own schedule
     // issues each ds_read one MFMA ahead, so every MFMA waits out the LDS latency)
     v8s kfr[SD][4];
@@ -575,6 +601,19 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
         const v8s kf = MMPT_ATTN_DIAG == 3 ? qf[0][(ks + kt) & (KS - 1)] : kfr[ks % SD][kt];
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) s[qt][kt] = mfma(kf, qf[qt][ks], s[qt][kt]);
+      }
+      if constexpr (DROP) {
+        // the 4·QT Philox calls of the block spread over its k-steps, each in the same scheduling
+        // region as that step's MFMAs (VALU integer work under the matrix pipe)
+#pragma unroll
+        for (int c = 0; c < 4 * QT; ++c)
+          if (c * KS / (4 * QT) == ks) {
+            const int qt = c / 4, kt = c % 4;
+            if (!CAUSAL || k0 + kt * 16 <= q0 + wave * 16 * QT + qt * 16 + 15) {  // (wave-uniform)
+              const philox4 W = drop_block(p, myq[qt] >> 2, (k0 + kt * 16 + 4 * g) >> 2, bh);
+              dkeep[qt][kt] = drop_word(W, fl & 3);
+            }
+          }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -645,7 +684,10 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float e = __builtin_amdgcn_exp2f(fmaf(s[qt][kt][i], sl2, nm));
-          s[qt][kt][i] = e;
+          // DROP: the row sum (and lse) are the undropped softmax's; the dropped P is zeroed
+          // before the bf16 pack, 1 / (1 - p_eff) goes into the O epilogue
+          if constexpr (DROP) s[qt][kt][i] = drop_keep(dkeep[qt][kt], i, p.dt8) ? e : 0.f;
+          else s[qt][kt][i] = e;
           rs += e;
         }
       l[qt] += rs;  // lane-partial row sum (this lane's 16 keys); reduced once at the end
@@ -714,7 +756,8 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_fwd_kernel(AttnParams p) {
   constexpr int CPR = D / 8, RPI = 64 / CPR, SWM = (CPR < 16 ? CPR : 16) - 1;
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    const float inv = l[qt] > 0.f ? 1.0f / l[qt] : 0.f;
+    float inv = l[qt] > 0.f ? 1.0f / l[qt] : 0.f;
+    if constexpr (DROP) inv *= p.dscale;
     const int r = qt * 16 + (lane & 15);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
@@ -804,13 +847,15 @@ constexpr int dkdv_slots() { return D == 256 ? MMPT_ATTN_DKDV_NS : 4; }
 // workgroups per CU the ring's LDS allows (2 also halves the register budget: KT = 1 only)
 template <int D>
 constexpr int dkdv_occ() { return dkdv_slots<D>() * (2 * 32 * D * 2 + 256) <= 80 * 1024 ? 2 : 1; }
-template <int D, bool CAUSAL, int KT, int NW, bool DS = false, int DR = D, bool VL = false>
+template <int D, bool CAUSAL, int KT, int NW, bool DS = false, int DR = D, bool VL = false,
+          bool DROP = false>
 __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_kernel(AttnParams p) {
   using I = Img<D>;
   constexpr int KS = dr_ksteps<D, DR>(), DT = DR / 16;
   constexpr int QB = 32, NS = dkdv_slots<D>();
   static_assert(!DS || (KT == 2 && QB == 32), "dS tiles: 32 keys per wave, 32-query blocks");
   static_assert(!(DS && VL), "dS tiles are indexed by the dense geometry");
+  static_assert(!(DS && DROP), "the dQ-from-dS kernel has no dropout");
   // register-ring depths of the S/dP phase (row fragments) and the dV/dK phase (transposed)
   constexpr int PA = MMPT_ATTN_BPA, PB = MMPT_ATTN_BPB;
   constexpr int KW = 16 * KT;            // keys per wave
@@ -919,6 +964,8 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
     // reads of step u + PA - 1 are in flight under the MFMAs of step u — hipcc's own order
     // waits out the LDS latency before every step, the only wave on its SIMD idle meanwhile
     constexpr int NSA = 2 * KS;
+    // DROP: the blocks of (queries q0 + 16qt + 4g + i, key mykey[kt]): word i, byte key & 3
+    philox4 dkw[DROP ? KT : 1][2] = {};
     v8s qfr[PA], dfr[PA];
 #pragma unroll
     for (int u = 0; u < PA - 1; ++u) {
@@ -944,6 +991,16 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
         }
         s[kt][qt] = mfma(qfr[u % PA], kf[kt][ks], s[kt][qt]);
         dp[kt][qt] = mfma(dfr[u % PA], vf[kt][ks], dp[kt][qt]);
+      }
+      if constexpr (DROP) {
+        // the 2·KT Philox calls of the block spread over its 2·KS steps, beside the MFMAs
+#pragma unroll
+        for (int c = 0; c < 2 * KT; ++c)
+          if (c * NSA / (2 * KT) == u) {
+            const int kt_ = c / 2, qt_ = c % 2;
+            dkw[kt_][qt_] = drop_block(p, (q0 + qt_ * 16 + 4 * g) >> 2, mykey[kt_] >> 2,
+                                       b * p.H + j * p.G + gi);
+          }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -974,6 +1031,13 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
           if (masked) {
             const int q = q0 + qt * 16 + 4 * g + i;
             if (q >= S || mykey[kt] >= S || (CAUSAL && mykey[kt] > q)) pr = 0.f;
+          }
+          if constexpr (DROP) {
+            // dV takes keep∘P (1 / (1 - p_eff) in its epilogue), dS = P∘(s·keep·dP − δ)
+            const bool keep = ((dkw[kt][qt].w[i] >> (8 * (mykey[kt] & 3))) & 0xFFu) >= p.dt8;
+            s[kt][qt][i] = keep ? pr : 0.f;
+            dp[kt][qt][i] = pr * ((keep ? dp[kt][qt][i] * p.dscale : 0.f) - dlv[i]);
+            continue;
           }
           s[kt][qt][i] = pr;                                // P
           dp[kt][qt][i] = pr * (dp[kt][qt][i] - dlv[i]);   // dS (unscaled)
@@ -1063,6 +1127,7 @@ __global__ __launch_bounds__(NW * 64, dkdv_occ<D>()) void attn_bwd_dkdv_ring_ker
       u.x = (uint32_t)f2bf(dk[kt][dt][0] * p.scale) | ((uint32_t)f2bf(dk[kt][dt][1] * p.scale) << 16);
       u.y = (uint32_t)f2bf(dk[kt][dt][2] * p.scale) | ((uint32_t)f2bf(dk[kt][dt][3] * p.scale) << 16);
       stage_w8(st + r * I::RB, c ^ (r & SWM), g & 1, r, u);
+      if constexpr (DROP) dv[kt][dt] *= p.dscale;
       u.x = (uint32_t)f2bf(dv[kt][dt][0]) | ((uint32_t)f2bf(dv[kt][dt][1]) << 16);
       u.y = (uint32_t)f2bf(dv[kt][dt][2]) | ((uint32_t)f2bf(dv[kt][dt][3]) << 16);
       stage_w8(st + (KW + r) * I::RB, c ^ (r & SWM), g & 1, r, u);
@@ -1498,7 +1563,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv_pair_kernel(AttnParams p
 // double-buffered in LDS by LDS-DMA.  Persistent like the forward (attn_item order): the
 // next item's first K/V block is staged under the current item's last key block, dQ leaves
 // through the LDS buffer that block frees, as 16-B row segments.
-template <int D, bool CAUSAL, int QT, int NW, int DR = D, bool VL = false>
+template <int D, bool CAUSAL, int QT, int NW, int DR = D, bool VL = false, bool DROP = false>
 __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
   using I = Img<D>;
   constexpr int KS = dr_ksteps<D, DR>(), DT = DR / 16;
@@ -1623,6 +1688,20 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
     for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) s[qt][kt] = dp[qt][kt] = v4f{0.f, 0.f, 0.f, 0.f};
+    // DROP: the keep bytes of (query myq[qt], keys k0 + 16kt + 4g + i), byte i — ahead of the
+    // MFMAs they do not depend on, so the scheduler can run the integer work beside them; a tile
+    // wholly above the diagonal draws nothing
+    uint32_t dkeep[DROP ? QT : 1][4] = {};
+    if constexpr (DROP) {
+#pragma unroll
+      for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+          if (!CAUSAL || k0 + kt * 16 <= q0 + wave * 16 * QT + qt * 16 + 15) {  // (wave-uniform)
+            const philox4 W = drop_block(p, myq[qt] >> 2, (k0 + kt * 16 + 4 * g) >> 2, bh);
+            dkeep[qt][kt] = drop_word(W, lane & 3);
+          }
+    }
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -1645,7 +1724,11 @@ __global__ __launch_bounds__(NW * 64, 1) void attn_bwd_dq_kernel(AttnParams p) {
           const int key = k0 + kt * 16 + 4 * g + i;
           float pr = exp2f(s[qt][kt][i] * sl2 - my_lse[qt]);
           if (key >= LEN(vsl) || myq[qt] >= LEN(vsl) || (CAUSAL && key > myq[qt])) pr = 0.f;
-          dp[qt][kt][i] = pr * (dp[qt][kt][i] - my_del[qt]);
+          if constexpr (DROP)  // dS = P∘(s·keep·dP − δ)
+            dp[qt][kt][i] = pr * ((drop_keep(dkeep[qt][kt], i, p.dt8) ? dp[qt][kt][i] * p.dscale : 0.f) -
+                                  my_del[qt]);
+          else
+            dp[qt][kt][i] = pr * (dp[qt][kt][i] - my_del[qt]);
         }
       dsf[qt][0] = pack_pair(dp[qt][0], dp[qt][1]);
       dsf[qt][1] = pack_pair(dp[qt][2], dp[qt][3]);
@@ -1887,9 +1970,9 @@ int g_attn_native80 = -1;
 int attn_native80() { return env_switch(g_attn_native80, "MMPT_ATTN_NATIVE80"); }
 // every entry's plan (attn_plan.h) is taken under these: the one place the switches are read
 AttnPlan plan_for(int64_t batch, int64_t seq, int64_t heads, int64_t head_dim, bool varlen,
-                  int64_t rot_dims = 0, bool tables_aligned = false) {
+                  int64_t rot_dims = 0, bool tables_aligned = false, bool dropout = false) {
   const AttnSwitches sw{attn_ds_mode(), attn_pair_mode(), attn_native80()};
-  return attn_plan(batch, seq, heads, head_dim, varlen, rot_dims, tables_aligned, sw);
+  return attn_plan(batch, seq, heads, head_dim, varlen, rot_dims, tables_aligned, sw, dropout);
 }
 
 // Wave layout per head dim: D = 256 -> 8 waves x 16 query rows (2 waves per SIMD: one
@@ -1958,18 +2041,18 @@ int by_head_dim(const AttnPlan& pl, F f) {
   return f(integral_constant<int, 128>{}, integral_constant<int, 128>{});  // 96, 112: padded to 128
 }
 
-template <int D, int DR, bool VL>
+template <int D, int DR, bool VL, bool DROP = false>
 int run_fwd(const AttnParams& p, bool causal, hipStream_t s) {
   constexpr int QT = qtiles<D>(), NW = qwaves<D>();
   const long items = (long)((p.S + NW * 16 * QT - 1) / (NW * 16 * QT)) * p.B * p.H;
   by_causal(causal, [&](auto c) {
-    constexpr auto kern = attn_fwd_kernel<D, c(), QT, NW, DR, VL>;
+    constexpr auto kern = attn_fwd_kernel<D, c(), QT, NW, DR, VL, DROP>;
     kern<<<persistent_grid<kern, D>(NW * 64, items), NW * 64, 0, s>>>(p);
   });
   return check_launch("attention_fwd");
 }
 
-template <int D, int DR, bool VL>
+template <int D, int DR, bool VL, bool DROP = false>
 int run_bwd(AttnParams p, const AttnPlan& plan, bool causal, float* delta, hipStream_t s) {
   const long rows = (long)p.B * p.S * p.H;
   constexpr int RPB = 4 * (64 / (D / 8));  // (t, h) rows per 256-thread block
@@ -1985,7 +2068,7 @@ int run_bwd(AttnParams p, const AttnPlan& plan, bool causal, float* delta, hipSt
   const long items = (long)((p.S + NW * 16 * QT - 1) / (NW * 16 * QT)) * p.B * p.H;
   // The family is the plan's.  The guard only keeps the other instantiations from naming kernels
   // they do not have: the dS families exist at D = 256, dense, two key tiles per wave.
-  if constexpr (D == 256 && KT == 2 && !VL) {
+  if constexpr (D == 256 && KT == 2 && !VL && !DROP) {
     if (plan.family != RING_RECOMPUTE) {
       // dS tiles: the dK/dV kernel writes them, dQ = scale · dS·K reads them
       const dim3 gq((p.S + 127) / 128, p.B * p.H);
@@ -2007,8 +2090,8 @@ int run_bwd(AttnParams p, const AttnPlan& plan, bool causal, float* delta, hipSt
     }
   }
   by_causal(causal, [&](auto c) {
-    attn_bwd_dkdv_ring_kernel<D, c(), KT, KNW, false, DR, VL><<<grid, KNW * 64, 0, s>>>(p);
-    constexpr auto dq = attn_bwd_dq_kernel<D, c(), QT, NW, DR, VL>;
+    attn_bwd_dkdv_ring_kernel<D, c(), KT, KNW, false, DR, VL, DROP><<<grid, KNW * 64, 0, s>>>(p);
+    constexpr auto dq = attn_bwd_dq_kernel<D, c(), QT, NW, DR, VL, DROP>;
     dq<<<persistent_grid<dq, D>(NW * 64, items), NW * 64, 0, s>>>(p);
   });
   return check_launch("attention_bwd");
@@ -2018,12 +2101,15 @@ int run_bwd(AttnParams p, const AttnPlan& plan, bool causal, float* delta, hipSt
 template <bool VL>
 int launch_fwd(const AttnParams& p, const AttnPlan& plan, bool causal, void* stream) {
   return by_head_dim(plan, [&](auto D, auto DR) {
+    if (plan.dropout) return run_fwd<D(), DR(), VL, true>(p, causal, (hipStream_t)stream);
     return run_fwd<D(), DR(), VL>(p, causal, (hipStream_t)stream);
   });
 }
 template <bool VL>
 int launch_bwd(const AttnParams& p, const AttnPlan& plan, bool causal, void* workspace, void* stream) {
   return by_head_dim(plan, [&](auto D, auto DR) {
+    if (plan.dropout)
+      return run_bwd<D(), DR(), VL, true>(p, plan, causal, (float*)workspace, (hipStream_t)stream);
     return run_bwd<D(), DR(), VL>(p, plan, causal, (float*)workspace, (hipStream_t)stream);
   });
 }
@@ -2165,6 +2251,144 @@ extern "C" int mmpt_attention_varlen_bwd(int64_t batch, int64_t max_seq, int64_t
   const int rc = attn_params(p, plan, "attention_varlen_bwd", batch, max_seq, heads, kv_heads, head_dim,
                              qkv, ld, head_stride, k_offset, v_offset, scale, out, ld_out, lse, &vl, &bw);
   return rc ? rc : launch_bwd<true>(p, plan, causal, workspace, stream);
+}
+
+// ---- attention-probability dropout (include/mmpt.h "K19") ----
+// The checks the drop entries add; t8 = the 8-bit threshold (0: the call is the plain entry's).
+static int drop_check(const char* entry, double p, int64_t max_seq, int64_t batch, int64_t heads,
+                      uint32_t& t8) {
+  MMPT_REQUIRE(p >= 0.0 && p < 1.0, "%s: p must lie in [0, 1), got %g", entry, p);
+  t8 = attn_dropout_t8(p);
+  if (t8 > 0 && max_seq > ATTN_DROPOUT_MAX_SEQ) {
+    set_error("%s: max_seq %lld > %lld with dropout on (16-bit block indices)", entry,
+              (long long)max_seq, (long long)ATTN_DROPOUT_MAX_SEQ);
+    return MMPT_ERR_UNSUPPORTED;
+  }
+  MMPT_REQUIRE(t8 == 0 || batch * heads < (1LL << 32), "%s: batch * heads must fit 32 bits", entry);
+  return MMPT_OK;
+}
+static void drop_params(AttnParams& ap, double p, uint64_t seed, uint64_t site) {
+  ap.dseed = seed;
+  ap.dsite = site;
+  ap.dt8 = attn_dropout_t8(p);
+  ap.dscale = attn_dropout_scale(p);
+}
+
+extern "C" double mmpt_attn_dropout_p_eff(double p) { return attn_dropout_p_eff(p); }
+
+extern "C" int mmpt_attention_drop_fwd(int64_t batch, int64_t max_seq, int64_t total_tokens,
+                                       int64_t heads, int64_t kv_heads, int64_t head_dim,
+                                       const void* qkv, int64_t ld, int64_t head_stride,
+                                       int64_t k_offset, int64_t v_offset, int causal, float scale,
+                                       const int32_t* cu_seqlens, void* out, int64_t ld_out,
+                                       float* lse, double p, uint64_t seed, uint64_t site,
+                                       void* stream) {
+  uint32_t t8;
+  int rc = drop_check("attention_drop_fwd", p, max_seq, batch, heads, t8);
+  if (rc) return rc;
+  const bool varlen = cu_seqlens != nullptr;
+  MMPT_REQUIRE(varlen || total_tokens == batch * max_seq,
+               "attention_drop_fwd: dense call (null cu_seqlens) with total_tokens %lld != batch * seq",
+               (long long)total_tokens);
+  if (t8 == 0) {
+    if (!varlen)
+      return mmpt_attention_gqa_fwd(batch, max_seq, heads, kv_heads, head_dim, qkv, ld, head_stride,
+                                    k_offset, v_offset, causal, scale, out, ld_out, lse, stream);
+    return mmpt_attention_varlen_fwd(batch, max_seq, total_tokens, heads, kv_heads, head_dim, qkv, ld,
+                                     head_stride, k_offset, v_offset, causal, scale, cu_seqlens, out,
+                                     ld_out, lse, stream);
+  }
+  const AttnPlan plan = plan_for(batch, max_seq, heads, head_dim, varlen, 0, false, true);
+  const AttnVarlen vl{cu_seqlens, total_tokens};
+  AttnParams ap;
+  rc = attn_params(ap, plan, "attention_drop_fwd", batch, max_seq, heads, kv_heads, head_dim, qkv, ld,
+                   head_stride, k_offset, v_offset, scale, out, ld_out, lse, varlen ? &vl : nullptr,
+                   nullptr);
+  if (rc) return rc;
+  drop_params(ap, p, seed, site);
+  return varlen ? launch_fwd<true>(ap, plan, causal, stream) : launch_fwd<false>(ap, plan, causal, stream);
+}
+
+// With dropout on: δ only (the ring dK/dV + recomputing dQ kernels at every head dim).  t8 == 0:
+// what the plain entry of the same form asks for.
+extern "C" int64_t mmpt_attention_drop_bwd_workspace_bytes(int64_t batch, int64_t max_seq,
+                                                           int64_t heads, int64_t head_dim,
+                                                           int varlen, double p) {
+  const bool on = p >= 0.0 && p < 1.0 && attn_dropout_t8(p) > 0;
+  return plan_for(batch, max_seq, heads, head_dim, varlen != 0, 0, false, on).workspace_bytes;
+}
+
+extern "C" int mmpt_attention_drop_bwd(int64_t batch, int64_t max_seq, int64_t total_tokens,
+                                       int64_t heads, int64_t kv_heads, int64_t head_dim,
+                                       const void* qkv, int64_t ld, int64_t head_stride,
+                                       int64_t k_offset, int64_t v_offset, int causal, float scale,
+                                       const int32_t* cu_seqlens, const void* out, const void* dout,
+                                       int64_t ld_out, const float* lse, void* dqkv, void* workspace,
+                                       double p, uint64_t seed, uint64_t site, void* stream) {
+  uint32_t t8;
+  int rc = drop_check("attention_drop_bwd", p, max_seq, batch, heads, t8);
+  if (rc) return rc;
+  const bool varlen = cu_seqlens != nullptr;
+  MMPT_REQUIRE(varlen || total_tokens == batch * max_seq,
+               "attention_drop_bwd: dense call (null cu_seqlens) with total_tokens %lld != batch * seq",
+               (long long)total_tokens);
+  if (t8 == 0) {
+    if (!varlen)
+      return mmpt_attention_gqa_bwd(batch, max_seq, heads, kv_heads, head_dim, qkv, ld, head_stride,
+                                    k_offset, v_offset, causal, scale, out, dout, ld_out, lse, dqkv,
+                                    workspace, stream);
+    return mmpt_attention_varlen_bwd(batch, max_seq, total_tokens, heads, kv_heads, head_dim, qkv, ld,
+                                     head_stride, k_offset, v_offset, causal, scale, cu_seqlens, out,
+                                     dout, ld_out, lse, dqkv, workspace, stream);
+  }
+  const AttnPlan plan = plan_for(batch, max_seq, heads, head_dim, varlen, 0, false, true);
+  const AttnVarlen vl{cu_seqlens, total_tokens};
+  const AttnBwdOps bw{dout, dqkv, workspace};
+  AttnParams ap;
+  rc = attn_params(ap, plan, "attention_drop_bwd", batch, max_seq, heads, kv_heads, head_dim, qkv, ld,
+                   head_stride, k_offset, v_offset, scale, out, ld_out, lse, varlen ? &vl : nullptr, &bw);
+  if (rc) return rc;
+  drop_params(ap, p, seed, site);
+  return varlen ? launch_bwd<true>(ap, plan, causal, workspace, stream)
+                : launch_bwd<false>(ap, plan, causal, workspace, stream);
+}
+
+// Test hook: keep[b][h][q][k] = 1 / 0, one thread per 4 x 4 block
+namespace mmpt {
+namespace {
+__global__ __launch_bounds__(256) void attn_dropout_mask_kernel(int B, int H, int Sq, int Sk,
+                                                                uint32_t t8, uint64_t seed,
+                                                                uint64_t site, uint8_t* keep) {
+  const int nqb = (Sq + 3) >> 2, nkb = (Sk + 3) >> 2;
+  const long n = (long)B * H * nqb * nkb;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
+    const int kb = (int)(e % nkb), qb = (int)(e / nkb % nqb);
+    const long bh = e / nkb / nqb;
+    const philox4 W = attn_dropout_words((uint32_t)qb, (uint32_t)kb, (uint32_t)bh, site, seed);
+    for (int i = 0; i < 4; ++i)
+      for (int jj = 0; jj < 4; ++jj) {
+        const int q = 4 * qb + i, k = 4 * kb + jj;
+        if (q < Sq && k < Sk)
+          keep[(bh * Sq + q) * Sk + k] = (uint8_t)attn_dropout_keep(W, (uint32_t)q, (uint32_t)k, t8);
+      }
+  }
+}
+}  // namespace
+}  // namespace mmpt
+
+extern "C" int mmpt_attn_dropout_mask(int64_t batch, int64_t heads, int64_t seq_q, int64_t seq_k,
+                                      double p, uint64_t seed, uint64_t site, uint8_t* keep,
+                                      void* stream) {
+  MMPT_REQUIRE(p >= 0.0 && p < 1.0, "attn_dropout_mask: p must lie in [0, 1), got %g", p);
+  MMPT_REQUIRE(batch > 0 && heads > 0 && seq_q > 0 && seq_k > 0 && keep, "attn_dropout_mask: bad arguments");
+  MMPT_REQUIRE(seq_q <= ATTN_DROPOUT_MAX_SEQ && seq_k <= ATTN_DROPOUT_MAX_SEQ &&
+                   batch * heads < (1LL << 31),
+               "attn_dropout_mask: sizes out of range");
+  const int64_t n = batch * heads * ((seq_q + 3) / 4) * ((seq_k + 3) / 4);
+  const int64_t g = (n + 255) / 256, cap = (int64_t)cu_slots(nullptr) * 8;
+  attn_dropout_mask_kernel<<<(unsigned)(g > cap ? cap : g), 256, 0, (hipStream_t)stream>>>(
+      (int)batch, (int)heads, (int)seq_q, (int)seq_k, attn_dropout_t8(p), seed, site, keep);
+  return check_launch("attn_dropout_mask");
 }
 
 // δ (fp32 per query row), then at D = 256 the dS tiles: ceil(S/32)^2 tiles of 2 KiB per

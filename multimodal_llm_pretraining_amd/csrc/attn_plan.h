@@ -39,6 +39,7 @@ struct AttnPlan {
   // backward workspace: δ (fp32 per query row) at 0, then for the dS families the tiles at
   // ds_offset (256-B aligned; 0 when there are none)
   int64_t delta_bytes, ds_offset, workspace_bytes;
+  bool dropout;  // the DROP variants of the forward, ring dK/dV and recomputing dQ kernels
 };
 
 int64_t ds_offset(int64_t batch, int64_t seq, int64_t heads) {  // after δ, 256-B aligned
@@ -47,14 +48,18 @@ int64_t ds_offset(int64_t batch, int64_t seq, int64_t heads) {  // after δ, 256
 
 // seq: max_seq for a varlen call (the stride of δ).  rot_dims / tables_aligned: the rotary width
 // and 16-B alignment of both tables of an mmpt_attention_bwd_rope call, 0 / false elsewhere.
+// dropout: an mmpt_attention_drop_* call with a non-zero threshold — the ring dK/dV + recomputing
+// dQ pair at every head dim, dense or varlen (the dS families have no dropout), no fused rope.
 AttnPlan attn_plan(int64_t batch, int64_t seq, int64_t heads, int64_t head_dim, bool varlen,
-                   int64_t rot_dims, bool tables_aligned, const AttnSwitches& sw) {
+                   int64_t rot_dims, bool tables_aligned, const AttnSwitches& sw,
+                   bool dropout = false) {
   AttnPlan pl{};
   pl.D = head_dim == 64 ? 64 : head_dim == 256 ? 256 : 128;  // 80, 96, 112: the D = 128 kernels
   pl.DR = head_dim == 80 && sw.native80 ? 80 : pl.D;         // (96, 112: padded to 128)
   // (varlen runs the ring dK/dV + recomputing dQ pair at every head dim: the dS tiles and the
   // wave-pair kernel index by the dense geometry)
-  const bool ds = head_dim == 256 && !varlen && sw.ds;
+  const bool ds = head_dim == 256 && !varlen && sw.ds && !dropout;
+  pl.dropout = dropout;
   pl.family = !ds ? RING_RECOMPUTE : sw.pair ? PAIR_DS : RING_DS;
   pl.fused_rope = pl.family == PAIR_DS && rot_dims == FUSED_ROT && tables_aligned;
   pl.delta_bytes = batch * seq * heads * (int64_t)sizeof(float);

@@ -1,6 +1,7 @@
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel Random Numbers: As Easy as 1, 2, 3",
 // SC'11; the Random123 constants), host and device: the counter-based generator behind the
-// hidden-dropout kernels (dropout.hip).  A stand-alone header (no HIP include) so that a plain
+// hidden-dropout kernels (dropout.hip) and the attention-probability dropout of the
+// flash-attention kernels (attention.hip; the addressing further down).  A stand-alone header (no HIP include) so that a plain
 // C++ program can check it against the published known answers.
 //
 // The dropout addressing (include/mmpt.h "K16"): logical element e = row*h + col of a
@@ -52,5 +53,35 @@ MMPT_PHILOX_HD philox4 dropout_words(uint64_t q, uint64_t site, uint64_t seed) {
 inline uint32_t dropout_threshold(double p) { return (uint32_t)(uint64_t)(p * 4294967296.0); }
 // 1 / (1 - p) rounded once to fp32: the factor kept elements are multiplied by.
 inline float dropout_scale(double p) { return (float)(1.0 / (1.0 - p)); }
+
+// ---- attention-probability dropout (include/mmpt.h "K19") ----
+// The keep bit of probability (batch b, query head h, query position q, key position k) — positions
+// inside their sequence — is one byte of a 4 x 4 block (4 queries x 4 keys) drawn by one call:
+//   W = philox4x32_10(ctr = {(q>>2) | ((k>>2) << 16), b*heads + h, lo32(site), hi32(site)},
+//                     key = {lo32(seed), hi32(seed)})
+//   byte = (W.w[q & 3] >> (8 * (k & 3))) & 0xFF,   keep iff byte >= t8 = floor(p * 256)
+// so a lane holding 4 consecutive keys of one query (forward, dQ) and a lane holding 4 consecutive
+// queries of one key (dK/dV) both pay one call per 4 elements.
+constexpr int64_t ATTN_DROPOUT_MAX_SEQ = 262144;  // q >> 2 and k >> 2 are 16 bits each
+
+// The words of the block (q >> 2, k >> 2) = (qb, kb) of batch-head bh = b*heads + h.
+MMPT_PHILOX_HD philox4 attn_dropout_words(uint32_t qb, uint32_t kb, uint32_t bh, uint64_t site,
+                                          uint64_t seed) {
+  return philox4x32_10(qb | (kb << 16), bh, (uint32_t)site, (uint32_t)(site >> 32), (uint32_t)seed,
+                       (uint32_t)(seed >> 32));
+}
+// The keep bit of (q, k) given its block's words.
+MMPT_PHILOX_HD bool attn_dropout_keep(const philox4& w, uint32_t q, uint32_t k, uint32_t t8) {
+  return ((w.w[q & 3] >> (8 * (k & 3))) & 0xFFu) >= t8;
+}
+MMPT_PHILOX_HD bool attn_dropout_keep_at(uint32_t q, uint32_t k, uint32_t bh, uint64_t site,
+                                         uint64_t seed, uint32_t t8) {
+  return attn_dropout_keep(attn_dropout_words(q >> 2, k >> 2, bh, site, seed), q, k, t8);
+}
+// Host side: the 8-bit threshold, the probability it realises, and the fp32 factor of the kept
+// probabilities (from p_eff, so the estimator stays unbiased).  t8 == 0 (p < 1/256) is p = 0.
+inline uint32_t attn_dropout_t8(double p) { return (uint32_t)(p * 256.0); }
+inline double attn_dropout_p_eff(double p) { return attn_dropout_t8(p) / 256.0; }
+inline float attn_dropout_scale(double p) { return (float)(1.0 / (1.0 - attn_dropout_p_eff(p))); }
 
 }  // namespace mmpt

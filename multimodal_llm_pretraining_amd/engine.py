@@ -87,7 +87,8 @@ def sort_segments(ids: np.ndarray, rows: np.ndarray):
 # Hidden-dropout site ids (mmpt_dropout_*'s 64-bit `site`): | step 32 | rank 16 | unit 12 | k 4 |
 # bits.  unit: 0 = the text embedding, 1 + i = text layer i, VISION_UNIT = the ViT embedding,
 # VISION_UNIT + 1 + i = ViT layer i (so at most 2047 layers a side); k: the site inside the
-# unit (a layer: 0 = after the attention output projection, 1 = after the MLP).
+# unit (a layer: 0 = after the attention output projection, 1 = after the MLP, 2 = the
+# attention probabilities — the site of the mmpt_attention_drop_* calls, which share the seed).
 SITE_STEPS, SITE_RANKS, SITE_UNITS, SITE_KS = 1 << 32, 1 << 16, 1 << 12, 1 << 4
 VISION_UNIT = SITE_UNITS // 2
 
@@ -442,6 +443,7 @@ class Engine:
             if layers >= VISION_UNIT:
                 raise ValueError(f"{layers} layers: dropout_site numbers at most {VISION_UNIT - 1}")
         self._pt = self._pv = 0.0  # the probabilities of the micro-step in flight
+        self._pat = self._pav = 0.0  # ... of the attention-probability dropout (text, vision)
         self._dstep = 0
         if store.device.type == "cuda":
             store.refresh_transposed()
@@ -685,8 +687,11 @@ class Engine:
         self._pt = self.cfg.text.hidden_dropout if on and self.cfg.text is not None else 0.0
         self._pv = self.cfg.vision.hidden_dropout if on and self.cfg.multimodal and \
             not self.frozen else 0.0
+        self._pat = self.cfg.text.attn_dropout if on and self.cfg.text is not None else 0.0
+        self._pav = self.cfg.vision.attention_dropout if on and self.cfg.multimodal and \
+            not self.frozen else 0.0
         self._dstep = self.dropout_step
-        if need_grad and (self._pt > 0 or self._pv > 0):
+        if need_grad and max(self._pt, self._pv, self._pat, self._pav) > 0:
             self.dropout_step += 1
 
     def _drop_grad(self, d, p, unit, k, bias, out=None):
@@ -696,6 +701,22 @@ class Engine:
         K.dropout_bf16(d, out, p, self.dropout_seed, self._site(unit, k))
         K.colsum(out, self.s.g(bias), accumulate=True)
         return out
+
+    def _attn_drop_fwd(self, pa, unit, vl, qkv, B, S, H, Hk, D, hs, koff, voff, causal, a, lse):
+        """Attention with probability dropout pa at site k = 2 of `unit` (dense, or varlen over
+        the batch vl): the forward, and the checkpoint recompute, which redraws the same mask."""
+        geo = dict(batch=B, seq=S) if vl is None else \
+            dict(lens=vl.lens, cu_seqlens=vl.cu_seqlens, max_seq=S)
+        K.attention_drop_fwd(qkv, H, Hk, D, hs, koff, voff, causal, D ** -0.5, a, lse, pa,
+                             self.dropout_seed, self._site(unit, 2), **geo)
+
+    def _attn_drop_bwd(self, pa, unit, vl, qkv, B, S, H, Hk, D, hs, koff, voff, causal, a, da, lse,
+                       dqkv):
+        """Backward of _attn_drop_fwd (same site); the caller runs the rope inverse afterwards."""
+        geo = dict(batch=B, seq=S) if vl is None else \
+            dict(lens=vl.lens, cu_seqlens=vl.cu_seqlens, max_seq=S)
+        K.attention_drop_bwd(qkv, H, Hk, D, hs, koff, voff, causal, D ** -0.5, a, da, lse, dqkv,
+                             pa, self.dropout_seed, self._site(unit, 2), **geo)
 
     def _text_layer_fwd(self, i, x, B, S):
         t = self.cfg.text
@@ -711,7 +732,10 @@ class Engine:
         a = self._e(T, h)
         lse = self._e(B * H * S, dtype=F32)
         vl = self._vl
-        if vl is None:
+        if self._pat > 0:
+            self._attn_drop_fwd(self._pat, 1 + i, vl, qkv, B, S, H, H, D, 3 * D, D, 2 * D, True, a,
+                                lse)
+        elif vl is None:
             K.attention_fwd(qkv, B, S, H, D, 3 * D, D, True, D ** -0.5, a, lse)
         else:
             K.attention_varlen_fwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, 3 * D, D, 2 * D, True,
@@ -769,7 +793,12 @@ class Engine:
         self._dw(dsa, a, p + "dense", bias=False)
         dqkv = self._e(T, 3 * h)
         vl = self._vl
-        if vl is not None:  # varlen: ring dK/dV + recomputing dQ, then the positional rope
+        if self._pat > 0:  # dropout: no fused rope backward, the rope inverse runs afterwards
+            self._attn_drop_bwd(self._pat, 1 + i, vl, qkv, B, S, H, H, D, 3 * D, D, 2 * D, True, a,
+                                da, lse, dqkv)
+            if t.rot_dims > 0:
+                self._rope(dqkv, S, H, D, t.rot_dims, 3 * D, D, inverse=True)
+        elif vl is not None:  # varlen: ring dK/dV + recomputing dQ, then the positional rope
             K.attention_varlen_bwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, 3 * D, D, 2 * D, True,
                                    D ** -0.5, a, da, lse, dqkv, max_seq=S)
             if t.rot_dims > 0:
@@ -807,7 +836,10 @@ class Engine:
         a = self._e(T, h)
         lse = self._e(B * H * S, dtype=F32)
         vl = self._vl
-        if vl is None:
+        if self._pat > 0:
+            self._attn_drop_fwd(self._pat, 1 + i, vl, qkv, B, S, H, Hk, D, D, H * D, (H + Hk) * D,
+                                True, a, lse)
+        elif vl is None:
             K.attention_gqa_fwd(qkv, B, S, H, Hk, D, H * D, (H + Hk) * D, True, D ** -0.5, a, lse)
         else:
             K.attention_varlen_fwd(qkv, vl.lens, vl.cu_seqlens, H, Hk, D, D, H * D, (H + Hk) * D,
@@ -848,7 +880,10 @@ class Engine:
         self._dw(d1, a, p + "dense", bias=False)
         dqkv = self._e(T, t.qkv_dim)
         vl = self._vl
-        if vl is None:
+        if self._pat > 0:
+            self._attn_drop_bwd(self._pat, 1 + i, vl, qkv, B, S, H, Hk, D, D, H * D, (H + Hk) * D,
+                                True, a, da, lse, dqkv)
+        elif vl is None:
             K.attention_gqa_bwd(qkv, B, S, H, Hk, D, H * D, (H + Hk) * D, True, D ** -0.5, a, da,
                                 lse, dqkv)
         else:
@@ -875,8 +910,11 @@ class Engine:
         qkv = self._linear(y1, p + "qkv")
         a = self._e(T, h)
         lse = self._e(B * H * Sv, dtype=F32)
-        K.attention_fwd(qkv, B, Sv, H, D, D, h, False, D ** -0.5, a, lse)
         pv, u = self._pv, VISION_UNIT + 1 + i
+        if self._pav > 0:
+            self._attn_drop_fwd(self._pav, u, None, qkv, B, Sv, H, H, D, D, h, 2 * h, False, a, lse)
+        else:
+            K.attention_fwd(qkv, B, Sv, H, D, D, h, False, D ** -0.5, a, lse)
         if pv > 0:  # h1 = x + drop(o): ViTSelfOutput.dropout
             h1 = self._e(T, h, dtype=F32)
             K.dropout_add_f32(self._linear(a, p + "o"), self._site(u, 0), x, h1, pv,
@@ -930,7 +968,11 @@ class Engine:
         da = self._dx(d1, p + "o")
         self._dw(d1, a, p + "o", bias=False)
         dqkv = self._e(T, 3 * h)
-        K.attention_bwd(qkv, B, Sv, H, D, D, h, False, D ** -0.5, a, da, lse, dqkv)
+        if self._pav > 0:
+            self._attn_drop_bwd(self._pav, u, None, qkv, B, Sv, H, H, D, D, h, 2 * h, False, a, da,
+                                lse, dqkv)
+        else:
+            K.attention_bwd(qkv, B, Sv, H, D, D, h, False, D ** -0.5, a, da, lse, dqkv)
         dy1 = self._dx(dqkv, p + "qkv")
         self._dw(dqkv, y1, p + "qkv")
         if i > 0:

@@ -434,6 +434,64 @@ def attention_varlen_bwd(qkv, lens, cu_seqlens, heads, kv_heads, head_dim, head_
               lse.data_ptr(), dqkv.data_ptr(), ws.data_ptr(), _stream())
 
 
+# ------------------------------------------------------- attention-probability dropout (K19)
+def attn_dropout_p_eff(p: float) -> float:
+    """The probability the 8-bit threshold realises: floor(p * 256) / 256."""
+    return float(_lib.query("mmpt_attn_dropout_p_eff", float(p)))
+
+
+def attn_dropout_mask(batch: int, heads: int, seq_q: int, seq_k: int, p: float, seed: int,
+                      site: int, device=None) -> torch.Tensor:
+    """Test hook: the keep mask uint8 [batch][heads][seq_q][seq_k] the drop entries apply."""
+    keep = torch.empty(batch, heads, seq_q, seq_k, dtype=torch.uint8,
+                       device=device or torch.device("cuda", torch.cuda.current_device()))
+    _lib.call("mmpt_attn_dropout_mask", batch, heads, seq_q, seq_k, float(p), int(seed),
+              int(site), keep.data_ptr(), _stream())
+    return keep
+
+
+def _drop_geometry(qkv, batch, seq, lens, cu_seqlens, max_seq):
+    """(batch, max_seq, total, cu pointer) of a drop call: dense (lens is None) or varlen."""
+    if lens is None:
+        if cu_seqlens is not None:
+            raise ValueError("attention_drop: cu_seqlens without lens")
+        return int(batch), int(seq), int(batch) * int(seq), None
+    b, mx, total = _varlen_args(qkv, lens, cu_seqlens, max_seq)
+    return b, mx, total, cu_seqlens.data_ptr()
+
+
+def attention_drop_fwd(qkv, heads, kv_heads, head_dim, head_stride, k_offset, v_offset, causal,
+                       scale, out, lse, p: float, seed: int, site: int, *, batch=None, seq=None,
+                       lens=None, cu_seqlens=None, max_seq: int | None = None) -> None:
+    """Attention with dropout on the probabilities (mask: include/mmpt.h K19).  Dense: batch, seq;
+    varlen: lens, cu_seqlens (as attention_varlen_fwd).  Layout arguments as
+    mmpt_attention_gqa_fwd.  lse is the undropped softmax's.  p < 1/256 is the plain entry."""
+    b, mx, total, cu = _drop_geometry(qkv, batch, seq, lens, cu_seqlens, max_seq)
+    if out.shape[0] < total or lse.numel() < b * heads * mx:
+        raise ValueError("attention_drop: out / lse too small")
+    _lib.call("mmpt_attention_drop_fwd", b, mx, total, heads, kv_heads, head_dim, qkv.data_ptr(),
+              _ld(qkv), head_stride, k_offset, v_offset, int(causal), float(scale), cu,
+              out.data_ptr(), _ld(out), lse.data_ptr(), float(p), int(seed), int(site), _stream())
+
+
+def attention_drop_bwd(qkv, heads, kv_heads, head_dim, head_stride, k_offset, v_offset, causal,
+                       scale, out, dout, lse, dqkv, p: float, seed: int, site: int, *, batch=None,
+                       seq=None, lens=None, cu_seqlens=None, max_seq: int | None = None) -> None:
+    """Backward of attention_drop_fwd with the same (p, seed, site).  No rope backward is fused:
+    rotate dqkv afterwards."""
+    b, mx, total, cu = _drop_geometry(qkv, batch, seq, lens, cu_seqlens, max_seq)
+    if min(out.shape[0], dout.shape[0], dqkv.shape[0]) < total or lse.numel() < b * heads * mx:
+        raise ValueError("attention_drop: out / dout / dqkv / lse too small")
+    if _ld(dqkv) != _ld(qkv) or _ld(dout) != _ld(out):
+        raise ValueError("attention_drop: dqkv / dout must have the row strides of qkv / out")
+    ws = workspace(_lib.query("mmpt_attention_drop_bwd_workspace_bytes", b, mx, heads, head_dim,
+                              int(cu is not None), float(p)), slot=3)
+    _lib.call("mmpt_attention_drop_bwd", b, mx, total, heads, kv_heads, head_dim, qkv.data_ptr(),
+              _ld(qkv), head_stride, k_offset, v_offset, int(causal), float(scale), cu,
+              out.data_ptr(), dout.data_ptr(), _ld(out), lse.data_ptr(), dqkv.data_ptr(),
+              ws.data_ptr(), float(p), int(seed), int(site), _stream())
+
+
 # ----------------------------------------------------------------------------- loss
 def cross_entropy(logits, labels, ignore_index: int, grad_scale: float, loss_rows,
                   dlogits=None, vocab_valid: int | None = None) -> None:

@@ -380,7 +380,8 @@ class MMPTForPretraining(nn.Module):
         self.engine.checkpointing = False
 
     def set_dropout_seed(self, seed: int) -> None:
-        """Key of the hidden-dropout masks (cfg.text / cfg.vision .hidden_dropout; default: the
+        """Key of the hidden- and attention-dropout masks (cfg.text / cfg.vision
+        .hidden_dropout, text.attn_dropout, vision.attention_dropout; default: the
         constructor's `seed`).  Dropout is active iff the module is in train() mode and p > 0;
         the masks also depend on the micro-step counter and the data-parallel rank
         (engine.dropout_site)."""
@@ -459,7 +460,8 @@ def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
             hidden_size=v.hidden, num_hidden_layers=v.layers, num_attention_heads=v.heads,
             intermediate_size=v.ffn, image_size=v.image, patch_size=v.patch,
             num_channels=v.channels, layer_norm_eps=v.eps, hidden_act="gelu", qkv_bias=True,
-            hidden_dropout_prob=v.hidden_dropout, attention_probs_dropout_prob=0.0,
+            hidden_dropout_prob=v.hidden_dropout,
+            attention_probs_dropout_prob=v.attention_dropout,
             num_labels=cfg.num_classes, attn_implementation="eager"))
     from transformers import GPTNeoXConfig, GPTNeoXForCausalLM
 
@@ -469,7 +471,8 @@ def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
                        rotary_pct=t.rotary_pct, rotary_emb_base=t.rope_theta,
                        max_position_embeddings=2048, use_parallel_residual=True,
                        hidden_act="gelu", layer_norm_eps=t.eps, tie_word_embeddings=False,
-                       hidden_dropout=t.hidden_dropout, attn_implementation="eager")
+                       hidden_dropout=t.hidden_dropout, attention_dropout=t.attn_dropout,
+                       attn_implementation="eager")
     if cfg.vision is None:
         return GPTNeoXForCausalLM(tc)
     from transformers import LlavaConfig, LlavaForConditionalGeneration, ViTConfig
@@ -477,7 +480,8 @@ def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
     v = cfg.vision
     vc = ViTConfig(hidden_size=v.hidden, num_hidden_layers=v.layers, num_attention_heads=v.heads,
                    intermediate_size=v.ffn, image_size=v.image, patch_size=v.patch,
-                   hidden_dropout_prob=v.hidden_dropout, attn_implementation="eager")
+                   hidden_dropout_prob=v.hidden_dropout,
+                   attention_probs_dropout_prob=v.attention_dropout, attn_implementation="eager")
     lc = LlavaConfig(vision_config=vc, text_config=tc, image_token_id=cfg.image_token_id,
                      vision_feature_layer=v.feature_layer,
                      vision_feature_select_strategy="default", projector_hidden_act="gelu")

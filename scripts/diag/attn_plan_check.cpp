@@ -8,7 +8,10 @@
 //   - fuse the rope backward only into the pair family, at 64 rotary dims, with aligned tables,
 //   - place the dS tiles 256-B aligned behind δ, and size the workspace by the closed form of
 //     include/mmpt.h (δ only for a varlen call, whatever the switches),
-//   - never let the bytes its family writes (δ, and the last dS tile's end) pass workspace_bytes.
+//   - never let the bytes its family writes (δ, and the last dS tile's end) pass workspace_bytes,
+//   - with dropout on (mmpt_attention_drop_*): the same D / DR, the ring dK/dV + recomputing dQ
+//     family, no fused rope and a δ-only workspace, whatever the switches, dense or varlen; and
+//     with it off exactly the plan of a call without the argument.
 // Exits non-zero with the offending cases printed.
 //
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
@@ -70,6 +73,20 @@ static void check_plan(const Case& c) {
   }
   if (c.varlen) CHECK(pl.workspace_bytes == delta && pl.family == RING_RECOMPUTE && !pl.fused_rope);
   CHECK(written <= pl.workspace_bytes);
+  CHECK(!pl.dropout);
+
+  const AttnPlan off = attn_plan(c.batch, c.seq, c.heads, c.head_dim, c.varlen, c.rot, c.aligned, c.sw,
+                                 false);
+  CHECK(off.D == pl.D && off.DR == pl.DR && off.family == pl.family &&
+        off.fused_rope == pl.fused_rope && off.delta_bytes == pl.delta_bytes &&
+        off.ds_offset == pl.ds_offset && off.workspace_bytes == pl.workspace_bytes && !off.dropout);
+  const AttnPlan dr = attn_plan(c.batch, c.seq, c.heads, c.head_dim, c.varlen, c.rot, c.aligned, c.sw,
+                                true);
+  ++checked;
+  CHECK(dr.dropout);
+  CHECK(dr.D == pl.D && dr.DR == pl.DR);
+  CHECK(dr.family == RING_RECOMPUTE && !dr.fused_rope);
+  CHECK(dr.delta_bytes == delta && dr.ds_offset == 0 && dr.workspace_bytes == delta);
 }
 
 int main() {

@@ -545,6 +545,97 @@ int mmpt_cls_ln_bwd(int64_t batch, int64_t tokens, int64_t h, const float* x, co
                     void* stream);
 
 /* ------------------------------------------------------------------------
+ * K20  post-LN encoder (RoBERTa, tf:models/roberta/modeling_roberta.py): LayerNorm AFTER the
+ * residual add, where every other model here normalises before its GEMMs.  fp32 statistics and
+ * outputs (autocast runs aten::layer_norm in fp32), one pass per sub-layer where composing
+ * mmpt_dropout_add_f32 + mmpt_layernorm_f32_fwd + mmpt_cast_f32_bf16 takes three.  The dropout
+ * masks are K16's: element row*h + col of `site`, same keep rule and scale, so
+ * mmpt_dropout_mask(site) describes them; p = 0 draws nothing.  Reductions over rows (dw, db,
+ * dsum, dtype) are per-workgroup partials summed in a fixed order by a second kernel: no
+ * atomics, bitwise reproducible.  Added without a change of MMPT_ABI_VERSION: the entries are
+ * new, nothing existing changed.
+ * rows in [1, 2^31), h % 8 == 0 and h <= 4096, 16-B aligned pointers, leading dimensions
+ * multiples of 8 and >= h, 0 <= p < 1; else MMPT_ERR_ARG (nothing is launched).
+ * ---------------------------------------------------------------------- */
+/* RobertaSelfOutput / RobertaOutput.forward: `LayerNorm(dropout(dense(x)) + input_tensor)`.
+ *   s   = resid + f32(drop(v; p, seed, site))   v bf16 [rows][ld_v]: bf16(f32(v) * scale) or +0
+ *                                               (one rounding, mmpt_dropout_bf16), one fp32 add
+ *   y32 = LN(s; w, b, eps)                      fp32; the row arithmetic of
+ *                                               mmpt_layernorm_f32_fwd: the same bits on the same s
+ *   y16 = bf16(y32)                             the next GEMM's operand
+ * resid, s, y32 dense fp32 [rows][h]; s may alias resid; y16 bf16 [rows][ld_y16]; mean, rstd
+ * fp32 [rows]. */
+int mmpt_add_layernorm_fwd(int64_t rows, int64_t h, float eps, const float* resid, const void* v,
+                           int64_t ld_v, const float* w, const float* b, float* s, float* y32,
+                           void* y16, int64_t ld_y16, float* mean, float* rstd, double p,
+                           uint64_t seed, uint64_t site, void* stream);
+int64_t mmpt_add_layernorm_bwd_workspace_bytes(int64_t rows, int64_t h);
+/* Its backward, as autograd under autocast produces it.  The gradient of the LayerNorm's output
+ *   dy   = dy32 + f32(dyb)     dy32 (fp32 dense, nullable): from the next residual add; dyb (bf16
+ *                              [rows][ld_dyb], nullable): the input gradient of the GEMM that
+ *                              read bf16(y); at least one of the two, one fp32 add when both
+ *   ds32 = LN'(dy; s, mean, rstd, w)            fp32, goes on down the residual; may alias dy32
+ *   dvb  = drop(bf16(ds32); p, seed, site)      bf16 [rows][ld_dvb]: the branch Linear's output
+ *                                               gradient, two roundings as ATen's
+ *   dw  += Σ_rows dy · x̂,  db += Σ_rows dy      fp32 (nullable)
+ *   dsum (and dsum2) += f32(bf16(Σ_rows f32(dvb)))   (nullable; dsum2 needs dsum): the branch
+ *                              Linear's bias gradient, fp32 sum of the masked bf16 tensor rounded
+ *                              to bf16 once (mmpt_layernorm_bwd_ex's dsum convention)
+ * workspace >= mmpt_add_layernorm_bwd_workspace_bytes. */
+int mmpt_add_layernorm_bwd(int64_t rows, int64_t h, const float* s, const float* mean,
+                           const float* rstd, const float* w, const float* dy32, const void* dyb,
+                           int64_t ld_dyb, float* ds32, void* dvb, int64_t ld_dvb, float* dw,
+                           float* db, float* dsum, float* dsum2, double p, uint64_t seed,
+                           uint64_t site, void* workspace, void* stream);
+/* RobertaEmbeddings.forward: gather, sum, LayerNorm and dropout in one pass.
+ *   e   = (word[ids[r]] + type_row) + pos_table[pos[r]]   fp32, HF's order (inputs_embeds +
+ *                              token_type_embeddings, then + position_embeddings); type_row is
+ *                              token_type_embeddings row 0 (type_vocab_size 1)
+ *   y   = LN(e; w, b, eps)     fp32, the row arithmetic of mmpt_layernorm_f32_fwd
+ *   h32 = drop(y; p, seed, site)   fp32: y * scale or +0 (mmpt_dropout_f32)
+ *   h16 = bf16(h32)
+ * e is not kept: the backward gathers it again.  ids int64 [rows] in [0, vocab), pos int64
+ * [rows] in [0, max_pos) (ids outside are clamped: validate on the host); h32 fp32, h16 bf16,
+ * both dense [rows][h]. */
+int mmpt_roberta_embed_fwd(int64_t rows, int64_t h, float eps, const int64_t* ids,
+                           const int64_t* pos, const float* word, int64_t vocab,
+                           const float* pos_table, int64_t max_pos, const float* type_row,
+                           const float* w, const float* b, float* h32, void* h16, float* mean,
+                           float* rstd, double p, uint64_t seed, uint64_t site, void* stream);
+int64_t mmpt_roberta_embed_bwd_workspace_bytes(int64_t rows, int64_t h);
+/*   dy   = drop(dh + f32(dhb); p, seed, site)   fp32 (the forward's map on the gradient); dh fp32
+ *                              dense: from the first residual add; dhb (bf16 dense, nullable):
+ *                              the input gradient of the GEMM that read h16
+ *   de   = LN'(dy; e, mean, rstd, w)            fp32 dense, may alias dh; e gathered again
+ *   dw  += Σ_rows dy · x̂,  db += Σ_rows dy,  dtype += Σ_rows de   fp32, no bf16 rounding: the
+ *                              embedding tables sit outside autocast (all nullable)
+ * de then goes to the word and the position table through mmpt_embed_segments /
+ * mmpt_embed_bwd_split keyed by ids and by pos (skip_id = padding_idx). */
+int mmpt_roberta_embed_bwd(int64_t rows, int64_t h, const int64_t* ids, const int64_t* pos,
+                           const float* word, int64_t vocab, const float* pos_table,
+                           int64_t max_pos, const float* type_row, const float* mean,
+                           const float* rstd, const float* w, const float* dh, const void* dhb,
+                           float* de, float* dw, float* db, float* dtype, double p, uint64_t seed,
+                           uint64_t site, void* workspace, void* stream);
+/* RobertaLMHead.layer_norm, which reads the bf16 GELU output g [rows][ld_g]:
+ *   n16 = bf16(LN(f32(g); w, b, eps))           bf16 [rows][ld_n16]: the decoder's operand
+ * (the statistics within an fp32 ulp of mmpt_layernorm_f32_fwd's on f32(g), not its bits) */
+int mmpt_mlm_ln_fwd(int64_t rows, int64_t h, float eps, const void* g, int64_t ld_g,
+                    const float* w, const float* b, void* n16, int64_t ld_n16, float* mean,
+                    float* rstd, void* stream);
+int64_t mmpt_mlm_ln_bwd_workspace_bytes(int64_t rows, int64_t h);
+/*   dg   = bf16(LN'(f32(dn16); f32(g), mean, rstd, w))     the LayerNorm's bf16 input gradient
+ *   dpre = bf16(dg · gelu'(pre))                bf16 [rows][ld_dpre]: the head dense's output
+ *                                               gradient (MMPT_EPI_BF16_DGELU's arithmetic;
+ *                                               pre = the dense's bf16 pre-activation)
+ *   dw  += Σ_rows dn · x̂,  db += Σ_rows dn      fp32 (nullable)
+ *   dsum += f32(bf16(Σ_rows f32(dpre)))         the head dense's bias gradient (nullable) */
+int mmpt_mlm_ln_bwd(int64_t rows, int64_t h, const void* g, int64_t ld_g, const float* mean,
+                    const float* rstd, const float* w, const void* dn16, int64_t ld_dn16,
+                    const void* pre, int64_t ld_pre, void* dpre, int64_t ld_dpre, float* dw,
+                    float* db, float* dsum, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------
  * ZeRO++ quantized communication (sharding = "zero_3++"): replaces DeepSpeed's
  * `zero_quantized_weights` / `zero_quantized_gradients` kernels that
  * src/train.py:196-201 switches on.  Blockwise symmetric quantization, 256-element

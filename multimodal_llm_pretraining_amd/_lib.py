@@ -106,6 +106,15 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_cls_ln_fwd": (I32, [I64, I64, I64, F32, P, P, P, P, I64, P, P, P]),
     "mmpt_cls_ln_bwd_workspace_bytes": (I64, [I64, I64]),
     "mmpt_cls_ln_bwd": (I32, [I64, I64, I64, P, P, P, P, I64, P, P, P, P, P, P, P, P]),
+    "mmpt_add_layernorm_fwd": (I32, [I64, I64, F32, P, P, I64, P, P, P, P, P, I64, P, P, F64, U64, U64, P]),
+    "mmpt_add_layernorm_bwd_workspace_bytes": (I64, [I64, I64]),
+    "mmpt_add_layernorm_bwd": (I32, [I64, I64, P, P, P, P, P, P, I64, P, P, I64, P, P, P, P, F64, U64, U64, P, P]),
+    "mmpt_roberta_embed_fwd": (I32, [I64, I64, F32, P, P, P, I64, P, I64, P, P, P, P, P, P, P, F64, U64, U64, P]),
+    "mmpt_roberta_embed_bwd_workspace_bytes": (I64, [I64, I64]),
+    "mmpt_roberta_embed_bwd": (I32, [I64, I64, P, P, P, I64, P, I64, P, P, P, P, P, P, P, P, P, P, F64, U64, U64, P, P]),
+    "mmpt_mlm_ln_fwd": (I32, [I64, I64, F32, P, I64, P, P, P, I64, P, P, P]),
+    "mmpt_mlm_ln_bwd_workspace_bytes": (I64, [I64, I64]),
+    "mmpt_mlm_ln_bwd": (I32, [I64, I64, P, I64, P, P, P, P, I64, P, I64, P, I64, P, P, P, P, P]),
 }
 
 

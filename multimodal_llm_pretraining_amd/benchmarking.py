@@ -88,6 +88,11 @@ class ManualTrainer:
                 f"sharding {sharding!r} for the vision-only classifier "
                 f"{C.preset_name(model.mmpt_config)!r} is not implemented (data parallel and "
                 "zero_1 are)")
+        if sharding_to_mode(sharding) in ("zero2", "zero3") and model.mmpt_config.text.roberta:
+            raise NotImplementedError(  # before partition_out releases the module's storage
+                f"sharding {sharding!r} for the roberta masked LM "
+                f"{C.preset_name(model.mmpt_config)!r} is not implemented (data parallel and "
+                "zero_1 are)")
         if sharding_to_mode(sharding) in ("zero2", "zero3") and \
                 not model.mmpt_config.freeze_tower_and_llm:
             # ZeRO-2/3 partition the fp32 master, gradients and optimizer state (ZeRO-3 the

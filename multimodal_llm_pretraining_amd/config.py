@@ -75,7 +75,12 @@ class TextConfig:
     partial RoPE, fused per-head q|k|v with biases, erf-GELU MLP, untied lm_head.
     arch "llama": Llama-3 (tf:models/llama, the LLM of the reference's llava-pretrain,
     src/models/llava.py:25) — sequential residual, RMSNorm, GQA (kv_heads), full RoPE with
-    the llama3 frequency scaling, SwiGLU MLP, no biases, lm_head tied to the embedding."""
+    the llama3 frequency scaling, SwiGLU MLP, no biases, lm_head tied to the embedding.
+    arch "roberta": RoBERTa masked LM (tf:models/roberta, the reference's src/models/roberta.py) —
+    post-LN encoder (LayerNorm after each residual add), learned positions counted from
+    pad_id + 1 over the non-pad ids, a LayerNorm over the summed word / position / type
+    embeddings, non-causal attention, erf-GELU MLP, the MLM head (dense, GELU, LayerNorm, the
+    decoder tied to the embedding plus a bias of its own), no label shift."""
 
     hidden: int = 2048
     layers: int = 16
@@ -100,6 +105,11 @@ class TextConfig:
     # attention_dropout as on VisionConfig: tests/test_dropout_cpu.py pins that a TextConfig has
     # no attribute of that name
     attn_dropout: float = 0.0
+    # arch "roberta": RobertaConfig.max_position_embeddings / pad_token_id (the padding_idx of the
+    # word and position tables) / type_vocab_size
+    max_positions: int = 0
+    pad_id: int = 1
+    type_vocab: int = 1
 
     def __post_init__(self):
         _check_dropout(self.hidden_dropout, "TextConfig")
@@ -107,6 +117,14 @@ class TextConfig:
         if self.hidden_dropout > 0 and self.arch == "llama":
             raise ValueError("hidden_dropout > 0 on a Llama text model: LlamaConfig has no "
                              "hidden dropout")
+        if self.arch == "roberta":
+            if self.rotary_pct != 0 or not self.tie_embeddings or self.kv_heads:
+                raise ValueError("arch 'roberta': rotary_pct 0, tied embeddings, no GQA")
+            if self.type_vocab != 1:
+                raise ValueError("arch 'roberta': type_vocab_size 1 only (token_type_ids are zero)")
+            if not 0 <= self.pad_id < self.n_vocab or self.max_positions < self.pad_id + 3:
+                raise ValueError("arch 'roberta': pad_id must be a vocabulary id and max_positions "
+                                 "at least pad_id + 3")
 
     @property
     def head_dim(self) -> int:
@@ -119,6 +137,16 @@ class TextConfig:
     @property
     def llama(self) -> bool:
         return self.arch == "llama"
+
+    @property
+    def roberta(self) -> bool:
+        return self.arch == "roberta"
+
+    def check_seq(self, seq: int) -> None:
+        """RoBERTa's position ids reach seq + pad_id: a longer sequence has no table row."""
+        if self.roberta and seq + self.pad_id + 1 > self.max_positions:
+            raise ValueError(f"sequence length {seq} needs {seq + self.pad_id + 1} position rows; "
+                             f"max_positions is {self.max_positions}")
 
     @property
     def n_kv(self) -> int:
@@ -271,6 +299,20 @@ PRESETS["tiny-llava-frozen"] = ModelConfig(text=PRESETS["tiny-llava"].text,
                                            image_token_id=1024, freeze_tower_and_llm=True)
 
 
+def _roberta(h, L, H, F, V, V_valid, max_pos, drop=0.0):
+    return TextConfig(hidden=h, layers=L, heads=H, ffn=F, vocab=V, vocab_valid=V_valid,
+                      rotary_pct=0.0, eps=1e-5, arch="roberta", tie_embeddings=True,
+                      hidden_dropout=drop, attn_dropout=drop, max_positions=max_pos)
+
+
+# the reference's `roberta` (src/models/roberta.py: RobertaConfig.from_pretrained("roberta-large")):
+# 24 layers, hidden 1024, 16 heads of 64, FFN 4096, 514 positions, vocabulary 50265 padded to
+# 50272 rows (16-B GEMM rows; the padding takes no part in the softmax), both dropouts 0.1
+PRESETS["roberta-large"] = ModelConfig(text=_roberta(1024, 24, 16, 4096, 50272, 50265, 514, 0.1))
+PRESETS["tiny-roberta"] = ModelConfig(text=_roberta(128, 2, 2, 256, 520, 515, 66))
+PRESETS["tiny-roberta-drop"] = ModelConfig(text=_roberta(128, 2, 2, 256, 520, 515, 66, 0.1))
+
+
 def with_dropout(cfg: ModelConfig, text: float = 0.0, vision: float = 0.0, *,
                  text_attention: float = 0.0, vision_attention: float = 0.0) -> ModelConfig:
     """`cfg` with the dropout probabilities set.  Hidden dropout: `text` on a GPTNeoX language
@@ -370,6 +412,31 @@ def param_shapes(cfg: ModelConfig) -> dict[str, tuple[int, ...]]:
         if not t.tie_embeddings:
             s["text.lm_head"] = (t.vocab, t.hidden)
         return s
+    if t.roberta:
+        s["text.pos_embed"] = (t.max_positions, t.hidden)
+        s["text.type_embed"] = (t.type_vocab, t.hidden)
+        s["text.embed_ln.weight"] = (t.hidden,)
+        s["text.embed_ln.bias"] = (t.hidden,)
+        for i in range(t.layers):
+            p = f"text.layers.{i}."
+            s[p + "qkv.weight"] = (3 * t.hidden, t.hidden)  # query | key | value
+            s[p + "qkv.bias"] = (3 * t.hidden,)
+            s[p + "dense.weight"] = (t.hidden, t.hidden)    # attention.output.dense
+            s[p + "dense.bias"] = (t.hidden,)
+            s[p + "ln1.weight"] = (t.hidden,)               # attention.output.LayerNorm
+            s[p + "ln1.bias"] = (t.hidden,)
+            s[p + "fc1.weight"] = (t.ffn, t.hidden)         # intermediate.dense
+            s[p + "fc1.bias"] = (t.ffn,)
+            s[p + "fc2.weight"] = (t.hidden, t.ffn)         # output.dense
+            s[p + "fc2.bias"] = (t.hidden,)
+            s[p + "ln2.weight"] = (t.hidden,)               # output.LayerNorm
+            s[p + "ln2.bias"] = (t.hidden,)
+        s["text.mlm.dense.weight"] = (t.hidden, t.hidden)   # lm_head.dense
+        s["text.mlm.dense.bias"] = (t.hidden,)
+        s["text.mlm.ln.weight"] = (t.hidden,)               # lm_head.layer_norm
+        s["text.mlm.ln.bias"] = (t.hidden,)
+        s["text.mlm.bias"] = (t.vocab,)                     # lm_head.bias (the decoder's)
+        return s
     for i in range(t.layers):
         p = f"text.layers.{i}."
         s[p + "ln1.weight"] = (t.hidden,)
@@ -411,6 +478,14 @@ def _classifier_flops(cfg: ModelConfig) -> float:
     return 3.0 * fwd
 
 
+def _roberta_flops(t: TextConfig, S: int) -> float:
+    """3 × (layers · (2S·h·(4h + 2F) + 4S²h) + the head's dense 2S·h² + the decoder over the real
+    vocabulary 2S·h·V_valid): every row is scored and the attention is square, so the executed
+    count is the reference-convention one."""
+    layer = 2 * S * t.hidden * (4 * t.hidden + 2 * t.ffn) + 4 * S * S * t.hidden
+    return 3.0 * (t.layers * layer + 2 * S * t.hidden * t.hidden + 2 * S * t.hidden * t.n_vocab)
+
+
 def flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     """Algorithmic fwd+bwd FLOPs per sample in the reference's convention
     (src/benchmarking/flops.py:9-37: FlopCounterMode over one fwd+bwd, eager
@@ -422,6 +497,8 @@ def flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     if cfg.classifier:
         return _classifier_flops(cfg)
     t = cfg.text
+    if t.roberta:
+        return _roberta_flops(t, seq_text)
     S = seq_text + (cfg.vision.num_patches if cfg.vision else 0)
     if t.llama:  # q,o: h^2 each; k,v: h*kv_dim each; gate, up, down: h*F each
         kvd = t.n_kv * t.head_dim
@@ -453,6 +530,8 @@ def executed_flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     if cfg.classifier:
         return _classifier_flops(cfg)
     t = cfg.text
+    if t.roberta:
+        return _roberta_flops(t, seq_text)
     n_img = cfg.vision.num_patches if cfg.vision else 0
     S = seq_text + n_img
     scored = seq_text - 1 if cfg.vision else S  # text-only batches keep every row (<5% unscored)

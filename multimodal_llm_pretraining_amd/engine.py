@@ -20,6 +20,10 @@ A vision-only classifier (ModelConfig.classifier: ViTForImageClassification,
 tf:models/vit/modeling_vit.py) runs the same ViT encoder, then the final LayerNorm on the CLS
 rows, the classifier GEMM and the cross entropy over one row per image (_cls_forward /
 _cls_backward).
+
+A masked LM (TextConfig.arch "roberta": RobertaForMaskedLM, tf:models/roberta/modeling_roberta.py)
+is a post-LN encoder: LayerNorm after each residual add (include/mmpt.h K20), learned positions,
+the MLM head on the labelled rows (_roberta_forward / _roberta_backward).
 """
 
 from __future__ import annotations
@@ -128,6 +132,14 @@ class Batch:
     or a mask without zeros), which is then object for object what it was without the
     argument.  B stays the number of sequences, S the padded width.
 
+    Masked-LM batches (TextConfig.arch "roberta"): no label shift — the label of row r is the
+    target of row r — and `pos_ids` (int64 [T]): HF's create_position_ids_from_input_ids over the
+    padded [B, S] ids, cumsum(id != pad_id) * (id != pad_id) + pad_id, so an id equal to pad_id
+    inside a sequence sits at position pad_id and does not advance the count; the positions of the
+    valid tokens do not depend on dropped right pads.  `pos_segments` are the position table's
+    embedding-backward segments (keyed by position id); both tables skip pad_id, their
+    padding_idx.
+
     Image batches (a vision-only classifier, ModelConfig.classifier): `input_ids` is None,
     `pixel_values` is [B, C, S, S] and `labels` [B] holds one class per image, each in
     [0, num_classes).  num_items = B; S / T count the ViT tokens (patches + CLS)."""
@@ -145,6 +157,8 @@ class Batch:
         if input_ids is None:
             raise ValueError("a language model needs input_ids")
         self.B, self.S = input_ids.shape
+        cfg.text.check_seq(self.S)
+        self.pos_ids, self.pos_segments = None, ()
         if cfg.multimodal and pixel_values is None:
             raise ValueError("multimodal model needs pixel_values")
         self.T, self.max_len = self.B * self.S, self.S
@@ -198,6 +212,7 @@ class Batch:
         self.labels = self.loss_labels = _to(lab, device, torch.int64)
         self.pixels = _to(pixel_values, device, F32)
         self.segments = ()
+        self.pos_ids, self.pos_segments = None, ()
 
     def _check_mask(self, attention_mask):
         """None for the dense path (no mask, or no zero in it); else the host bool [B, S] mask,
@@ -240,6 +255,8 @@ class Batch:
         if cfg.multimodal:
             self.pixels = _to(pixel_values, device, F32)
         self.segments = self._segments(cfg, device)
+        if cfg.text.roberta:
+            self.pos_segments = self._segments(cfg, device, self.pos_ids, cfg.text.max_positions)
 
     def use(self, stream) -> None:
         """Order `stream` after the staging stream and hand the staged tensors to it (the
@@ -248,7 +265,8 @@ class Batch:
             return
         stream.wait_event(self._ready)
         for t in (self.ids, self.labels, self.loss_rows, self.loss_labels, self.loss_map,
-                  self.img_map, self.pixels, self.cu_seqlens, self.pos, *self.segments):
+                  self.img_map, self.pixels, self.cu_seqlens, self.pos, self.pos_ids,
+                  *self.segments, *self.pos_segments):
             if t is not None:
                 t.record_stream(stream)
         self._ready = None
@@ -258,12 +276,20 @@ class Batch:
         lab = labels.to(torch.int64)
         if mask is not None:  # HF's Llava loss drops the labels under the mask
             lab = lab.masked_fill(~mask, -100)
-        shifted = torch.full_like(lab, -100)
-        shifted[:, :-1] = lab[:, 1:]  # ForCausalLMLoss: pad(labels, (0,1)) then [..., 1:]
+        if cfg.text.roberta:  # masked LM: the label of a row is its own target
+            shifted = lab
+            pos_ids = _roberta_pos_ids(input_ids.to(torch.int64), cfg.text.pad_id).reshape(-1)
+        else:
+            shifted = torch.full_like(lab, -100)
+            shifted[:, :-1] = lab[:, 1:]  # ForCausalLMLoss: pad(labels, (0,1)) then [..., 1:]
         shifted = shifted.reshape(-1)
         if mask is not None:  # drop the pads: everything below is over the T valid tokens
             sel = mask.reshape(-1)
             ids, shifted = ids[sel], shifted[sel]
+            if cfg.text.roberta:
+                pos_ids = pos_ids[sel]
+        if cfg.text.roberta:
+            self.pos_ids = _to(pos_ids, device, torch.int64)
         idn = ids.numpy()
         if idn.size and (idn.min() < 0 or idn.max() >= cfg.text.vocab):
             raise ValueError(f"token ids must lie in [0, {cfg.text.vocab})")
@@ -311,8 +337,14 @@ class Batch:
         lab = labels.to(device, torch.int64)
         if mask is not None:
             lab = lab.masked_fill(~mask, -100)
-        shifted = torch.full_like(lab, -100)
-        shifted[:, :-1] = lab[:, 1:]
+        if cfg.text.roberta:
+            shifted = lab
+            pos_ids = _roberta_pos_ids(input_ids.to(device, torch.int64), cfg.text.pad_id)
+            pos_ids = pos_ids.reshape(-1)
+            self.pos_ids = (pos_ids if sel is None else pos_ids[sel]).contiguous()
+        else:
+            shifted = torch.full_like(lab, -100)
+            shifted[:, :-1] = lab[:, 1:]
         self.labels = shifted.contiguous().view(-1)
         if sel is not None:
             self.labels = self.labels[sel].contiguous()
@@ -339,23 +371,33 @@ class Batch:
                 raise ValueError(f"image tokens {n_img} != features {expect}")
             self.img_map = torch.where(mask, mask.cumsum(0) - 1, -1).to(torch.int32).contiguous()
 
-    def _segments(self, cfg: ModelConfig, device) -> tuple:
+    def _segments(self, cfg: ModelConfig, device, keys=None, vocab=None) -> tuple:
         """Index bookkeeping for the deterministic embedding backward: the
         text rows stably sorted by token id, one segment per distinct id — built on the
         device by `mmpt_embed_segments` (seg_id, seg_off, perm, nseg, bad), the count left in
         HBM.  (A CPU `device` — host-logic tests only, the engine cannot run there — uses
         the numpy restatement `sort_segments`.)"""
         skip = cfg.image_token_id if cfg.multimodal else -1
+        if cfg.text.roberta:  # padding_idx of both tables: no gradient from the gather
+            skip = cfg.text.pad_id
+        keys = self.ids if keys is None else keys  # (the position table: keyed by position id)
+        vocab = cfg.text.vocab if vocab is None else vocab
         if device.type != "cuda":
-            ids = self.ids.to("cpu", torch.int64).numpy()
+            ids = keys.to("cpu", torch.int64).numpy()
             rows = np.arange(ids.size) if skip < 0 else np.flatnonzero(ids != skip)
             return tuple(torch.from_numpy(a) for a in sort_segments(ids, rows))
-        return K.embed_segments(self.ids, cfg.text.vocab, skip)
+        return K.embed_segments(keys, vocab, skip)
 
     @property
     def tokens(self) -> int:
         """Token rows the step computes over (the valid tokens of a padded batch)."""
         return self.T
+
+
+def _roberta_pos_ids(ids: torch.Tensor, pad_id: int) -> torch.Tensor:
+    """tf:models/roberta/modeling_roberta.py create_position_ids_from_input_ids over [B, S] ids."""
+    m = (ids != pad_id).to(torch.int64)
+    return torch.cumsum(m, dim=1) * m + pad_id
 
 
 def _check_labels(kept: np.ndarray, vocab_valid: int) -> None:
@@ -386,7 +428,7 @@ class Engine:
         self.dev = store.device
         t = cfg.text
         self.cos = self.sin = None  # a vision-only classifier has no rope
-        if t is not None:
+        if t is not None and not t.roberta:  # (RoBERTa: learned positions)
             if t.llama:
                 cos, sin = rope_tables_llama3(t.head_dim, t.rope_theta, t.rope_scaling, max_seq)
             else:
@@ -424,7 +466,8 @@ class Engine:
         # tower / language model, no backward through the tower at all
         self.frozen = cfg.freeze_tower_and_llm
         store.transposed = [n for n in store.shapes if len(store.shapes[n]) == 2 and
-                            n not in ("vision.patch.weight", "text.embed", "vision.pos")]
+                            n not in ("vision.patch.weight", "text.embed", "vision.pos",
+                                      "text.pos_embed", "text.type_embed")]
         if tied:  # the tied lm_head's input gradient reads E^T
             store.transposed.append("text.embed")
         if self.frozen and not t.llama:
@@ -526,6 +569,8 @@ class Engine:
         order += [f"text.layers.{i}" for i in range(cfg.text.layers)]
         if not cfg.text.tie_embeddings:
             order.append("text.lm_head")
+        if cfg.text.roberta:
+            order.append("text.mlm")
         return order
 
     def _ready(self, prefixes):
@@ -1135,12 +1180,204 @@ class Engine:
         self._join_side()
         self.cache.clear()
 
+    # -------------------------------------------------------------- RoBERTa (post-LN encoder)
+    # The stream between sub-layers is fp32 AND normalised: each sub-layer ends in
+    # LayerNorm(dropout(branch) + input) (include/mmpt.h K20).  A layer's input is the pair
+    # (h32, h16 = bf16(h32)): h32 feeds the residual add, h16 the GEMMs.  Kept for the backward,
+    # per sub-layer: the sum s the LayerNorm read (fp32), its statistics and its bf16 output; the
+    # fp32 output lives only until the next add.
+    def _roberta_attn(self, i, qkv, B, S, a, lse, da=None, dqkv=None):
+        """Non-causal attention over q | k | v (each `hidden` wide, head h at h * D), as the ViT
+        layer calls it: dense, varlen over a right-padded batch, or with probability dropout."""
+        t = self.cfg.text
+        h, H, D = t.hidden, t.heads, t.head_dim
+        vl, sc = self._vl, D ** -0.5
+        if da is None:
+            if self._pat > 0:
+                self._attn_drop_fwd(self._pat, 1 + i, vl, qkv, B, S, H, H, D, D, h, 2 * h, False, a,
+                                    lse)
+            elif vl is None:
+                K.attention_fwd(qkv, B, S, H, D, D, h, False, sc, a, lse)
+            else:
+                K.attention_varlen_fwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, D, h, 2 * h, False, sc,
+                                       a, lse, max_seq=S)
+        elif self._pat > 0:
+            self._attn_drop_bwd(self._pat, 1 + i, vl, qkv, B, S, H, H, D, D, h, 2 * h, False, a, da,
+                                lse, dqkv)
+        elif vl is None:
+            K.attention_bwd(qkv, B, S, H, D, D, h, False, sc, a, da, lse, dqkv)
+        else:
+            K.attention_varlen_bwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, D, h, 2 * h, False, sc, a,
+                                   da, lse, dqkv, max_seq=S)
+
+    def _roberta_layer_fwd(self, i, x, B, S):
+        """RobertaLayer (tf:models/roberta/modeling_roberta.py) under autocast:
+        h1 = LN1(f32(drop(dense(attn(bf16 x)))) + x);  h2 = LN2(f32(drop(fc2(gelu(fc1(bf16 h1))))) + h1)."""
+        t = self.cfg.text
+        x32, x16 = x
+        T, h, H = x32.shape[0], t.hidden, t.heads
+        p = f"text.layers.{i}."
+        pt, seed = self._pt, self.dropout_seed
+        ckpt = self.checkpointing and not self._recomputing
+        qkv = self._linear(x16, p + "qkv")
+        a = self._e(T, h)
+        lse = self._e(B * H * S, dtype=F32)
+        self._roberta_attn(i, qkv, B, S, a, lse)
+        ao = self._linear(a, p + "dense")
+        # the sum may overwrite the input stream unless that is this layer's checkpoint
+        s1 = self._e(T, h, dtype=F32) if ckpt else x32
+        h1, y1 = self._e(T, h, dtype=F32), self._e(T, h)
+        m1, r1 = self._e(T, dtype=F32), self._e(T, dtype=F32)
+        K.add_layernorm_fwd(x32, ao, self.s.p(p + "ln1.weight"), self.s.p(p + "ln1.bias"), t.eps,
+                            s1, h1, y1, m1, r1, pt, seed, self._site(1 + i, 0))
+        pre, act = self._e(T, t.ffn), self._e(T, t.ffn)
+        self._linear(y1, p + "fc1", out=pre, epi=K.EPI_BF16_GELU, out2=act)
+        mo = self._linear(act, p + "fc2")
+        h2, y2 = self._e(T, h, dtype=F32), self._e(T, h)
+        m2, r2 = self._e(T, dtype=F32), self._e(T, dtype=F32)
+        K.add_layernorm_fwd(h1, mo, self.s.p(p + "ln2.weight"), self.s.p(p + "ln2.bias"), t.eps,
+                            h1, h2, y2, m2, r2, pt, seed, self._site(1 + i, 1))  # s2 over h1
+        if ckpt:
+            self.cache[("t", i)] = ("ckpt", x)
+        else:
+            self.cache[("t", i)] = (x16, qkv, a, lse, s1, m1, r1, y1, pre, act, h1, m2, r2)
+        return h2, y2
+
+    def _roberta_layer_bwd(self, i, d32, dyb, B, S):
+        """d32: the fp32 gradient of the layer's output from the residual add above (None for the
+        top layer); dyb: the bf16 input gradient of the GEMM that read its bf16 copy.  Returns the
+        same pair for the layer's input."""
+        t = self.cfg.text
+        T, h = dyb.shape[0], t.hidden
+        p = f"text.layers.{i}."
+        pt, seed = self._pt, self.dropout_seed
+        self._side_fence()
+        self._unit_bwd(f"text.layers.{i}")
+        self._restore(("t", i), self._roberta_layer_fwd, i, B, S)
+        x16, qkv, a, lse, s1, m1, r1, y1, pre, act, s2, m2, r2 = self.cache.pop(("t", i))
+        g = self.s.g
+        ds = self._e(T, h, dtype=F32) if d32 is None else d32
+        dm = self._e(T, h)  # drop(bf16(ds2)): fc2's output gradient; + fc2.bias's gradient
+        K.add_layernorm_bwd(s2, m2, r2, self.s.p(p + "ln2.weight"), ds, dm, dy32=d32, dyb=dyb,
+                            dw=g(p + "ln2.weight"), db=g(p + "ln2.bias"), dsum=g(p + "fc2.bias"),
+                            p=pt, seed=seed, site=self._site(1 + i, 1))
+        dpre = self._dx_dgelu(dm, p + "fc2", pre, bias_of=p + "fc1")
+        self._dw(dm, act, p + "fc2", bias=False)
+        dy1 = self._dx(dpre, p + "fc1")
+        self._dw(dpre, y1, p + "fc1", bias=False)
+        do = self._e(T, h)  # drop(bf16(ds1)): dense's output gradient; + dense.bias's gradient
+        K.add_layernorm_bwd(s1, m1, r1, self.s.p(p + "ln1.weight"), ds, do, dy32=ds, dyb=dy1,
+                            dw=g(p + "ln1.weight"), db=g(p + "ln1.bias"), dsum=g(p + "dense.bias"),
+                            p=pt, seed=seed, site=self._site(1 + i, 0))
+        da = self._dx(do, p + "dense")
+        self._dw(do, a, p + "dense", bias=False)
+        dqkv = self._e(T, 3 * h)
+        self._roberta_attn(i, qkv, B, S, a, lse, da, dqkv)
+        dx16 = self._dx(dqkv, p + "qkv")
+        self._dw(dqkv, x16, p + "qkv")
+        self._unit_done(f"text.layers.{i}")
+        return ds, dx16
+
+    def _roberta_forward(self, batch: Batch, grad_scale: float, need_grad: bool) -> torch.Tensor:
+        """RobertaForMaskedLM: embeddings (gather + LayerNorm + dropout, one kernel), the post-LN
+        layers, then the MLM head on the labelled rows only: dense + GELU, LayerNorm, the decoder
+        (the tied embedding) with its bias, Σ CE over the real vocabulary."""
+        t = self.cfg.text
+        B, S, T, h = batch.B, batch.max_len, batch.T, t.hidden
+        self._vl = batch if batch.cu_seqlens is not None else None
+        if self.dev.type == "cuda":
+            batch.use(torch.cuda.current_stream(self.dev))
+        region = getattr(self.units, "region", None)
+        if region is not None:
+            region()
+        self._drop_begin(need_grad)
+        h32, h16 = self._e(T, h, dtype=F32), self._e(T, h)
+        m0, r0 = self._e(T, dtype=F32), self._e(T, dtype=F32)
+        K.roberta_embed_fwd(batch.ids, batch.pos_ids, self.s.p("text.embed"),
+                            self.s.p("text.pos_embed"), self.s.p("text.type_embed")[0],
+                            self.s.p("text.embed_ln.weight"), self.s.p("text.embed_ln.bias"), t.eps,
+                            h32, h16, m0, r0, self._pt, self.dropout_seed, self._site(0, 0))
+        x = (h32, h16)
+        for i in range(t.layers):
+            self._unit_fwd(f"text.layers.{i}")
+            x = self._roberta_layer_fwd(i, x, B, S)
+        self._unit_fwd("text.mlm")
+        xv = x[1]
+        if batch.loss_rows is not None:  # the head reads the labelled rows only
+            xv = self._e(batch.loss_rows.numel(), h)
+            K.gather_rows(x[1], batch.loss_rows, xv)
+        R = xv.shape[0]
+        pre, gl = self._e(R, h), self._e(R, h)
+        self._linear(xv, "text.mlm.dense", out=pre, epi=K.EPI_BF16_GELU, out2=gl)
+        n16 = self._e(R, h)
+        mh, rh = self._e(R, dtype=F32), self._e(R, dtype=F32)
+        K.mlm_ln_fwd(gl, self.s.p("text.mlm.ln.weight"), self.s.p("text.mlm.ln.bias"), t.eps, n16,
+                     mh, rh)
+        logits = self._e(R, t.vocab)
+        K.gemm(n16, self.s.w("text.embed"), logits, bias=self.s.w("text.mlm.bias"))
+        loss_rows = self._e(R, dtype=F32)
+        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
+                        logits if need_grad else None, vocab_valid=t.n_vocab)
+        loss = self._e(1, dtype=F32)
+        K.sum_f32(loss_rows, loss)
+        if need_grad:
+            self.cache["head"] = (xv, pre, gl, mh, rh, n16, logits)
+            self.cache["emb"] = (m0, r0)
+        else:
+            self.cache.clear()
+        return loss
+
+    def _roberta_backward(self, batch: Batch, scale: torch.Tensor | None) -> None:
+        t = self.cfg.text
+        B, S, T, h = batch.B, batch.max_len, batch.T, t.hidden
+        self._vl = batch if batch.cu_seqlens is not None else None
+        xv, pre, gl, mh, rh, n16, dlogits = self.cache.pop("head")
+        m0, r0 = self.cache.pop("emb")
+        if scale is not None:
+            dlogits.mul_(scale.to(torch.float32))
+        g = self.s.g
+        self._unit_bwd("text.mlm")
+        dn = self._dx(dlogits, "text.embed")  # through E^T (the decoder is the tied embedding)
+        self._dw(dlogits, n16, "text.embed", bias=False)
+        K.colsum(dlogits, g("text.mlm.bias"), accumulate=True)
+        del dlogits
+        dpre = self._e(xv.shape[0], h)
+        K.mlm_ln_bwd(gl, mh, rh, self.s.p("text.mlm.ln.weight"), dn, pre, dpre,
+                     dw=g("text.mlm.ln.weight"), db=g("text.mlm.ln.bias"),
+                     dsum=g("text.mlm.dense.bias"))
+        dyb = self._dx(dpre, "text.mlm.dense")
+        self._dw(dpre, xv, "text.mlm.dense", bias=False)
+        self._unit_done("text.mlm")
+        if batch.loss_map is not None:  # back to every row (zero where there is no label)
+            dyc, dyb = dyb, self._e(T, h)
+            K.expand_rows(dyc, batch.loss_map, dyb)
+        d32 = None
+        for i in reversed(range(t.layers)):
+            d32, dyb = self._roberta_layer_bwd(i, d32, dyb, B, S)
+        # the embeddings: dropout and LayerNorm backward over the re-gathered sum, the type row's
+        # gradient, then the two tables' deterministic scatter-adds (padding_idx rows skipped)
+        K.roberta_embed_bwd(batch.ids, batch.pos_ids, self.s.p("text.embed"),
+                            self.s.p("text.pos_embed"), self.s.p("text.type_embed")[0], m0, r0,
+                            self.s.p("text.embed_ln.weight"), d32, d32, dhb=dyb,
+                            dw=g("text.embed_ln.weight"), db=g("text.embed_ln.bias"),
+                            dtype=g("text.type_embed")[0], p=self._pt, seed=self.dropout_seed,
+                            site=self._site(0, 0))
+        if self._side is not None:  # the tied decoder's weight gradient also lands in text.embed
+            torch.cuda.current_stream(self.dev).wait_stream(self._side)
+        K.embed_bwd(batch.segments, d32, g("text.embed"))
+        K.embed_bwd(batch.pos_segments, d32, g("text.pos_embed"))
+        self._ready(("text.",))
+        self._join_side()
+        self.cache.clear()
+
     # -------------------------------------------------------------- whole model
     def forward(self, batch: Batch, grad_scale: float, need_grad: bool = True) -> torch.Tensor:
         """Returns Σ_tokens CE (device fp32 [1]); when need_grad, dlogits are written
         (scaled by grad_scale = 1/num_items of the global batch) and the caches kept."""
         if self.cfg.classifier:
             return self._cls_forward(batch, grad_scale, need_grad)
+        if self.cfg.text.roberta:
+            return self._roberta_forward(batch, grad_scale, need_grad)
         cfg, t = self.cfg, self.cfg.text
         # S: the longest sequence — the padded width on the dense path, where T = B * S
         B, S, T = batch.B, batch.max_len, batch.T
@@ -1194,6 +1431,8 @@ class Engine:
         (device scalar, e.g. autograd's grad_output) multiplies the loss gradient."""
         if self.cfg.classifier:
             return self._cls_backward(batch, scale)
+        if self.cfg.text.roberta:
+            return self._roberta_backward(batch, scale)
         cfg, t = self.cfg, self.cfg.text
         B, S, T = batch.B, batch.max_len, batch.T
         self._vl = batch if batch.cu_seqlens is not None else None

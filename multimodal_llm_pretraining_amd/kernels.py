@@ -758,3 +758,118 @@ def transpose_bf16(src, dst) -> None:
         raise ValueError("transpose: dst must be [cols, rows]")
     _lib.call("mmpt_transpose_bf16", rows, cols, src.data_ptr(), _ld(src), dst.data_ptr(),
               _ld(dst), _stream())
+
+
+# ----------------------------------------------------------------------------- post-LN (K20)
+# RoBERTa's LayerNorm-after-the-residual family (include/mmpt.h K20).  Every tensor is checked
+# here; a bad shape raises before anything is launched.
+def _dense(t, dtype, shape, name) -> None:
+    _check(t, dtype, name)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a dense {tuple(shape)} tensor, got {tuple(t.shape)}")
+
+
+def _rows_bf16(t, rows, h, name) -> int:
+    _check(t, torch.bfloat16, name)
+    if tuple(t.shape) != (rows, h):
+        raise ValueError(f"{name}: expected [{rows}, {h}], got {tuple(t.shape)}")
+    return _ld(t)
+
+
+def add_layernorm_fwd(resid, v, w, b, eps: float, s, y32, y16, mean, rstd, p: float = 0.0,
+                      seed: int = 0, site: int = 0) -> None:
+    """s = resid + f32(drop(v)); y32 = LN(s); y16 = bf16(y32); mean / rstd per row.  resid, s,
+    y32 dense fp32 [rows, h] (s may be resid); v, y16 bf16 (any row stride)."""
+    rows, h = resid.shape
+    for t, n in ((resid, "resid"), (s, "s"), (y32, "y32")):
+        _dense(t, torch.float32, (rows, h), "add_layernorm_fwd." + n)
+    ld_v = _rows_bf16(v, rows, h, "add_layernorm_fwd.v")
+    ld_y = _rows_bf16(y16, rows, h, "add_layernorm_fwd.y16")
+    _lib.call("mmpt_add_layernorm_fwd", rows, h, float(eps), resid.data_ptr(), v.data_ptr(), ld_v,
+              w.data_ptr(), b.data_ptr(), s.data_ptr(), y32.data_ptr(), y16.data_ptr(), ld_y,
+              mean.data_ptr(), rstd.data_ptr(), float(p), seed & _U64, site & _U64, _stream())
+
+
+def add_layernorm_bwd(s, mean, rstd, w, ds32, dvb, dy32=None, dyb=None, dw=None, db=None,
+                      dsum=None, dsum2=None, p: float = 0.0, seed: int = 0, site: int = 0) -> None:
+    """ds32 = LN'(dy32 + f32(dyb)) (may be dy32); dvb = drop(bf16(ds32)); dw / db += the LayerNorm's
+    parameter gradients; dsum (and dsum2) += bf16(Σ_rows dvb), the branch Linear's bias gradient."""
+    rows, h = s.shape
+    _dense(s, torch.float32, (rows, h), "add_layernorm_bwd.s")
+    _dense(ds32, torch.float32, (rows, h), "add_layernorm_bwd.ds32")
+    if dy32 is not None:
+        _dense(dy32, torch.float32, (rows, h), "add_layernorm_bwd.dy32")
+    ld_dyb = 0 if dyb is None else _rows_bf16(dyb, rows, h, "add_layernorm_bwd.dyb")
+    ld_dvb = _rows_bf16(dvb, rows, h, "add_layernorm_bwd.dvb")
+    ws = workspace(_lib.query("mmpt_add_layernorm_bwd_workspace_bytes", rows, h), slot=2)
+    _lib.call("mmpt_add_layernorm_bwd", rows, h, s.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+              w.data_ptr(), _p(dy32), _p(dyb), ld_dyb, ds32.data_ptr(), dvb.data_ptr(), ld_dvb,
+              _p(dw), _p(db), _p(dsum), _p(dsum2), float(p), seed & _U64, site & _U64,
+              ws.data_ptr(), _stream())
+
+
+def _embed_tables(ids, pos, word, pos_table, type_row, rows, h, name):
+    _check(ids, torch.int64, name + ".ids")
+    _check(pos, torch.int64, name + ".pos")
+    if ids.numel() != rows or pos.numel() != rows or not (ids.is_contiguous() and
+                                                          pos.is_contiguous()):
+        raise ValueError(f"{name}: ids / pos must be contiguous [{rows}] vectors")
+    for t, n in ((word, "word"), (pos_table, "pos_table")):
+        _check(t, torch.float32, f"{name}.{n}")
+        if t.dim() != 2 or t.shape[1] != h or not t.is_contiguous():
+            raise ValueError(f"{name}: {n} must be a dense [*, {h}] table")
+    _dense(type_row, torch.float32, (h,), name + ".type_row")
+
+
+def roberta_embed_fwd(ids, pos, word, pos_table, type_row, w, b, eps: float, h32, h16, mean, rstd,
+                      p: float = 0.0, seed: int = 0, site: int = 0) -> None:
+    """h32 = drop(LN((word[ids] + type_row) + pos_table[pos])), h16 = bf16(h32)."""
+    rows, h = h32.shape
+    _embed_tables(ids, pos, word, pos_table, type_row, rows, h, "roberta_embed_fwd")
+    _dense(h32, torch.float32, (rows, h), "roberta_embed_fwd.h32")
+    _dense(h16, torch.bfloat16, (rows, h), "roberta_embed_fwd.h16")
+    _lib.call("mmpt_roberta_embed_fwd", rows, h, float(eps), ids.data_ptr(), pos.data_ptr(),
+              word.data_ptr(), word.shape[0], pos_table.data_ptr(), pos_table.shape[0],
+              type_row.data_ptr(), w.data_ptr(), b.data_ptr(), h32.data_ptr(), h16.data_ptr(),
+              mean.data_ptr(), rstd.data_ptr(), float(p), seed & _U64, site & _U64, _stream())
+
+
+def roberta_embed_bwd(ids, pos, word, pos_table, type_row, mean, rstd, w, dh, de, dhb=None,
+                      dw=None, db=None, dtype=None, p: float = 0.0, seed: int = 0,
+                      site: int = 0) -> None:
+    """de = LN'(drop(dh + f32(dhb))) over the re-gathered embedding sum (de may be dh); dw / db /
+    dtype +=."""
+    rows, h = dh.shape
+    _embed_tables(ids, pos, word, pos_table, type_row, rows, h, "roberta_embed_bwd")
+    _dense(dh, torch.float32, (rows, h), "roberta_embed_bwd.dh")
+    _dense(de, torch.float32, (rows, h), "roberta_embed_bwd.de")
+    if dhb is not None:
+        _dense(dhb, torch.bfloat16, (rows, h), "roberta_embed_bwd.dhb")
+    ws = workspace(_lib.query("mmpt_roberta_embed_bwd_workspace_bytes", rows, h), slot=2)
+    _lib.call("mmpt_roberta_embed_bwd", rows, h, ids.data_ptr(), pos.data_ptr(), word.data_ptr(),
+              word.shape[0], pos_table.data_ptr(), pos_table.shape[0], type_row.data_ptr(),
+              mean.data_ptr(), rstd.data_ptr(), w.data_ptr(), dh.data_ptr(), _p(dhb), de.data_ptr(),
+              _p(dw), _p(db), _p(dtype), float(p), seed & _U64, site & _U64, ws.data_ptr(),
+              _stream())
+
+
+def mlm_ln_fwd(g, w, b, eps: float, n16, mean, rstd) -> None:
+    """n16 = bf16(LN(f32(g))): the MLM head's LayerNorm over the bf16 GELU output."""
+    rows, h = g.shape
+    ld_g = _rows_bf16(g, rows, h, "mlm_ln_fwd.g")
+    ld_n = _rows_bf16(n16, rows, h, "mlm_ln_fwd.n16")
+    _lib.call("mmpt_mlm_ln_fwd", rows, h, float(eps), g.data_ptr(), ld_g, w.data_ptr(),
+              b.data_ptr(), n16.data_ptr(), ld_n, mean.data_ptr(), rstd.data_ptr(), _stream())
+
+
+def mlm_ln_bwd(g, mean, rstd, w, dn16, pre, dpre, dw=None, db=None, dsum=None) -> None:
+    """dpre = bf16(bf16(LN'(dn16)) * gelu'(pre)); dw / db += ; dsum += bf16(Σ_rows dpre)."""
+    rows, h = g.shape
+    ld_g = _rows_bf16(g, rows, h, "mlm_ln_bwd.g")
+    ld_dn = _rows_bf16(dn16, rows, h, "mlm_ln_bwd.dn16")
+    ld_pre = _rows_bf16(pre, rows, h, "mlm_ln_bwd.pre")
+    ld_dp = _rows_bf16(dpre, rows, h, "mlm_ln_bwd.dpre")
+    ws = workspace(_lib.query("mmpt_mlm_ln_bwd_workspace_bytes", rows, h), slot=2)
+    _lib.call("mmpt_mlm_ln_bwd", rows, h, g.data_ptr(), ld_g, mean.data_ptr(), rstd.data_ptr(),
+              w.data_ptr(), dn16.data_ptr(), ld_dn, pre.data_ptr(), ld_pre, dpre.data_ptr(), ld_dp,
+              _p(dw), _p(db), _p(dsum), ws.data_ptr(), _stream())

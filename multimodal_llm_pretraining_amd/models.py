@@ -14,7 +14,8 @@ the LLaVA-pretrain recipe (src/models/llava.py:80-124) used for the C3 compositi
     configs (the reference's "naive" branch: eager attention); no fetch.
 `llava-pretrain` is the reference's own CLIP-L/14-336 + Llama-3.2-1B model (with its
 freeze); `vit` / `vit-bf16` its ViT-L/16 image classifier (src/models/vit.py); model types
-outside the path (roberta, mamba, convnext, llava-finetune, vilt-*) raise.
+`roberta` / `roberta-bf16` its RoBERTa-large masked LM (src/models/roberta.py); model types
+outside the path (mamba, convnext, llava-finetune, vilt-*) raise.
 """
 
 from __future__ import annotations
@@ -37,10 +38,11 @@ PythiaT = Literal["pythia-14m", "pythia-31m", "pythia-70m", "pythia-160m", "pyth
 VitPythiaT = Literal["vit-b16-pythia-1b", "clip-l14-336-pythia-2.8b"]
 LlavaT = Literal["llava-pretrain", "llava-pretrain-unfrozen"]
 ViTT = Literal["vit", "vit-bf16"]
-ModelT = Literal[PythiaT, VitPythiaT, LlavaT, ViTT]
+RobertaT = Literal["roberta", "roberta-bf16"]
+ModelT = Literal[PythiaT, VitPythiaT, LlavaT, ViTT, RobertaT]
 # reference model types that are not on this path (out of scope;
 # llava-finetune needs a private checkpoint, src/models/llava.py:151)
-OUT_OF_SCOPE = ("roberta", "mamba", "convnext-large-1k", "convnext-large-22k",
+OUT_OF_SCOPE = ("mamba", "convnext-large-1k", "convnext-large-22k",
                 "convnext-xlarge-22k", "llava-finetune",
                 "vilt-pretrain", "vilt-finetune", "vilt-original-pretrain",
                 "vilt-original-finetune")
@@ -257,6 +259,42 @@ class ViTModelClass(BaseModelClass):
         return DummyImageClassificationDataset(self.image_size, self.num_classes, num_samples)
 
 
+class RobertaModelClass(BaseModelClass):
+    """The reference's `roberta` (src/models/roberta.py:14-70): RobertaForMaskedLM on the
+    roberta-large config with eager attention; batch 8192, 500,000 steps, fp16, Adam lr 4e-4
+    β (0.9, 0.98) wd 0.01, linear schedule with 30,000 warmup steps, no clipping, sequences of
+    512 over a vocabulary of 50265.
+
+    `roberta` restates that recipe verbatim and, like the fp16 Pythias and `vit`, is a faithful
+    record that TrainingClass.build_trainer refuses: this path has bf16-autocast kernels only.
+    `roberta-bf16` is the same model and recipe under bf16 autocast — the runnable variant."""
+
+    def build_model(self, use_custom_kernels: bool = True) -> nn.Module:
+        if use_custom_kernels:
+            return MMPTForPretraining(self.model_config)
+        return build_hf_model(self.model_config)
+
+    @property
+    def model_config(self) -> C.ModelConfig:
+        return C.get_config("roberta-large")
+
+    batch_size = property(lambda self: 8192)
+    training_steps = property(lambda self: 500000)
+    mixed_precision = property(lambda self: "bf16" if self.model_type == "roberta-bf16" else "fp16")
+    optimizer = property(lambda self: torch.optim.Adam)
+    optimizer_kwargs = property(lambda self: {"lr": 4e-4, "betas": (0.9, 0.98),
+                                              "weight_decay": 0.01})
+    scheduler_type = property(lambda self: "linear")
+    scheduler_kwargs = property(lambda self: {"num_warmup_steps": 30_000})
+    max_grad_norm = property(lambda self: 0.0)
+    fsdp_layers_to_wrap = property(lambda self: ["RobertaLayer"])
+    vocab_size = property(lambda self: 50265)
+    sequence_length = property(lambda self: 512)
+
+    def load_dummy_dataset(self, num_samples: int = 50_000):
+        return DummyTextModelingDataset(self.vocab_size, self.sequence_length, num_samples)
+
+
 def get_model_class(model_type: str) -> BaseModelClass:
     """src/models/__init__.py:240-296 for the types on the MI355X path."""
     if model_type in PythiaModelClass._LR:
@@ -269,6 +307,8 @@ def get_model_class(model_type: str) -> BaseModelClass:
         return LlavaPretrainModelClass(model_type)
     if model_type in ("vit", "vit-bf16"):
         return ViTModelClass(model_type)
+    if model_type in ("roberta", "roberta-bf16"):
+        return RobertaModelClass(model_type)
     if model_type in OUT_OF_SCOPE:
         raise NotImplementedError(f"model type {model_type!r} is not on the MI355X hot path "
                                   "(SURVEY.md §8 scope)")
@@ -365,6 +405,10 @@ class MMPTForPretraining(nn.Module):
             self.config = SimpleNamespace(hidden_size=t.hidden, text_config=text_cfg,
                                           use_cache=False, model_type="mmpt",
                                           image_token_index=cfg.image_token_id)
+            if t.roberta:  # a text-only model: HF keeps these on the top-level config
+                self.config.vocab_size = t.n_vocab
+                self.config.max_position_embeddings = t.max_positions
+                self.config.pad_token_id = t.pad_id
         self.gradient_checkpointing = False
         self._shadow_version = self.store.master._version
 
@@ -463,9 +507,21 @@ def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
             hidden_dropout_prob=v.hidden_dropout,
             attention_probs_dropout_prob=v.attention_dropout,
             num_labels=cfg.num_classes, attn_implementation="eager"))
+    t = cfg.text
+    if t.roberta:
+        from transformers import RobertaConfig, RobertaForMaskedLM
+
+        # roberta-large's public hyper-parameters written out (no hub access); the vocabulary is
+        # the real one: the padding rows exist only in the HIP layout
+        return RobertaForMaskedLM(RobertaConfig(
+            vocab_size=t.n_vocab, hidden_size=t.hidden, num_hidden_layers=t.layers,
+            num_attention_heads=t.heads, intermediate_size=t.ffn, hidden_act="gelu",
+            hidden_dropout_prob=t.hidden_dropout, attention_probs_dropout_prob=t.attn_dropout,
+            max_position_embeddings=t.max_positions, type_vocab_size=t.type_vocab,
+            layer_norm_eps=t.eps, pad_token_id=t.pad_id, bos_token_id=0, eos_token_id=2,
+            attn_implementation="eager"))
     from transformers import GPTNeoXConfig, GPTNeoXForCausalLM
 
-    t = cfg.text
     tc = GPTNeoXConfig(vocab_size=t.vocab, hidden_size=t.hidden, num_hidden_layers=t.layers,
                        num_attention_heads=t.heads, intermediate_size=t.ffn,
                        rotary_pct=t.rotary_pct, rotary_emb_base=t.rope_theta,

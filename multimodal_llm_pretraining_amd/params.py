@@ -23,8 +23,9 @@ def is_fp32_read(name: str) -> bool:
     γ/β (fp32 under autocast), the token-embedding table (embedding lookups are not
     autocast) and the ViT CLS / position embeddings.  They are laid out first, in one
     contiguous region, so ZeRO can re-broadcast exactly that region after the update."""
-    return name in ("text.embed", "vision.pos", "vision.cls") or ".ln" in name \
-        or "final_ln" in name
+    return name in ("text.embed", "vision.pos", "vision.cls", "text.pos_embed",
+                    "text.type_embed") or ".ln" in name or "final_ln" in name \
+        or "embed_ln" in name
 
 
 class ParamStore:
@@ -204,7 +205,7 @@ def init_normal(store: ParamStore, seed: int = 0, std: float = 0.02, cfg=None) -
     g = torch.Generator().manual_seed(seed)
     for name, shape in store.shapes.items():
         if name.endswith(("ln1.weight", "ln2.weight", "final_ln.weight", "ln_pre.weight",
-                          "ln_post.weight")):
+                          "ln_post.weight", "embed_ln.weight", "mlm.ln.weight")):
             t = torch.ones(shape)
         else:
             t = torch.randn(shape, generator=g) * std
@@ -213,6 +214,11 @@ def init_normal(store: ParamStore, seed: int = 0, std: float = 0.02, cfg=None) -
             t[:, v.channels * v.patch * v.patch:] = 0
         if name in ("text.embed", "text.lm_head") and cfg is not None:
             t[cfg.text.n_vocab:] = 0  # vocabulary padding rows (never read, zero gradient)
+        if cfg is not None and cfg.text is not None and cfg.text.roberta:
+            if name in ("text.embed", "text.pos_embed"):
+                t[cfg.text.pad_id] = 0  # padding_idx rows (RobertaPreTrainedModel._init_weights)
+            if name == "text.mlm.bias":
+                t[cfg.text.n_vocab:] = 0  # the decoder bias of the vocabulary padding rows
         if name in ("cls_head.weight", "cls_head.bias") and cfg is not None:
             t[cfg.num_classes:] = 0  # class padding rows (outside the softmax, zero gradient)
         store.load({name: t})

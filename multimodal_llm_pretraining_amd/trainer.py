@@ -70,6 +70,12 @@ class ManualTrainer:
                 f"sharding {step_cfg.sharding!r} for the vision-only classifier "
                 f"{C.preset_name(self.cfg) or step_cfg.model!r} is not implemented (data "
                 "parallel and zero_1 are)")
+        if mode in ("zero2", "zero3") and self.cfg.text.roberta:
+            # the per-unit partition has no unit order for the post-LN layers and the MLM head
+            raise NotImplementedError(
+                f"sharding {step_cfg.sharding!r} for the roberta masked LM "
+                f"{C.preset_name(self.cfg) or step_cfg.model!r} is not implemented (data "
+                "parallel and zero_1 are)")
         if mode == "zero3" and self.cfg.text.tie_embeddings:
             raise NotImplementedError("ZeRO-3 with a tied lm_head (Llama) is not implemented")
         # ZeRO-2 and ZeRO-3 share the per-unit partition (zero3.py): ZeRO-2 keeps the bf16

@@ -53,6 +53,8 @@ def unit_of(name: str) -> str | None:
         return "text.lm_head"
     if name.startswith("cls_head."):
         return "cls_head"
+    if name.startswith("text.mlm."):  # RoBERTa's MLM head: dense and the decoder bias
+        return "text.mlm"
     raise KeyError(f"no ZeRO-3 unit for parameter {name!r}")
 
 

@@ -195,7 +195,7 @@ def train(output_dir: str, model_type: str, training_arguments: dict, max_steps:
                    num_warmup_steps=int(a.get("warmup_steps", 0)),
                    num_training_steps=int(a.get("max_steps", steps)),
                    min_lr_rate=float(sched_kw.get("min_lr_rate", 0.0))),
-        adam_from_args(a, mc), device)
+        adam_from_args(a, mc), device, model_cfg=mc.model_config)
     ds = mc.load_dummy_dataset()
     os.makedirs(output_dir, exist_ok=True)
     log = []

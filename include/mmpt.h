@@ -636,6 +636,69 @@ int mmpt_mlm_ln_bwd(int64_t rows, int64_t h, const void* g, int64_t ld_g, const 
                     float* db, float* dsum, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------
+ * K21  ConvNeXt (tf:models/convnext/modeling_convnext.py): the 7x7 depthwise convolution of
+ * ConvNextLayer (forward, input gradient, weight gradient), the layer-scale residual, the global
+ * average pool and the 2x2/s2 patch permutations that make ConvNextStage's downsample conv a
+ * GEMM.  Activations are NHWC: rows (b, y, x), columns c; H and W are separate arguments.
+ * Depthwise weights are tap-major [49][C], tap = ky*7 + kx (HF's [C][1][7][7] transposed), padding
+ * 3 with zeros outside the image — taps outside are predicated, never loaded.  Arithmetic is what
+ * autocast(bf16) produces: bf16 operands, fp32 accumulation, one bf16 rounding of a conv result;
+ * the fp32 residual stream and gamma stay fp32.  Reductions over rows are per-workgroup partials
+ * summed in a fixed order by a second kernel: no atomics, bitwise reproducible.  Added without a
+ * change of MMPT_ABI_VERSION: the entries are new, nothing existing changed.
+ * C % 8 == 0 and C <= 4096, B, H, W >= 1 (planes smaller than the filter included) with
+ * B*H*W < 2^31 (rows < 2^31), 16-B aligned pointers, leading dimensions multiples of 8 and >= C;
+ * else MMPT_ERR_ARG (nothing is launched).
+ * ---------------------------------------------------------------------- */
+/* c = bf16(Σ_taps bf16(x)[b, y+ky-3, x+kx-3, ch] * w[tap][ch] + bias[ch]), fp32 accumulation over
+ * the in-image taps.  x fp32 [B][H][W][C] (rounded to bf16 on the way in), w bf16 [49][C], bias
+ * bf16 [C], c bf16 [B][H][W][C]. */
+int mmpt_dwconv7_fwd(int64_t B, int64_t H, int64_t W, int64_t C, const float* x, const void* w,
+                     const void* bias, void* c, void* stream);
+/* dx_out = dx_in + f32(bf16(Σ_taps dc[b, y-ky+3, x-kx+3, ch] * w[tap][ch])).  dc bf16, dx_in fp32
+ * (NULL: taken as zero; may alias dx_out), dx_out fp32, all [B][H][W][C]. */
+int mmpt_dwconv7_bwd_input(int64_t B, int64_t H, int64_t W, int64_t C, const void* dc,
+                           const void* w, const float* dx_in, float* dx_out, void* stream);
+int64_t mmpt_dwconv7_bwd_weight_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t C);
+/* dw[tap][ch] += f32(bf16(Σ_{b,y,x} dc[b,y,x,ch] * bf16(x)[b, y+ky-3, x+kx-3, ch])),
+ * db[ch] += f32(bf16(Σ_{b,y,x} dc[b,y,x,ch])): fp32 sums, one bf16 rounding, then += into the
+ * fp32 gradients (the MMPT_EPI_F32_ACC convention).  dw fp32 [49][C], db fp32 [C]. */
+int mmpt_dwconv7_bwd_weight(int64_t B, int64_t H, int64_t W, int64_t C, const float* x,
+                            const void* dc, float* dw, float* db, void* workspace, void* stream);
+/* ConvNextLayer's residual: out = resid + gamma * f32(y), the product and the sum each rounded to
+ * fp32 (two roundings, as torch's mul then add).  resid, out fp32 dense [rows][C] (out may alias
+ * resid); gamma fp32 [C]; y bf16 [rows][ld_y]. */
+int mmpt_layerscale_add_fwd(int64_t rows, int64_t C, const float* resid, const float* gamma,
+                            const void* y, int64_t ld_y, float* out, void* stream);
+int64_t mmpt_layerscale_bwd_workspace_bytes(int64_t rows, int64_t C);
+/* dy = bf16(gamma * g) (bf16 [rows][ld_dy]); dgamma[c] += Σ_rows g * f32(y) in fp32 (gamma is an
+ * fp32 parameter outside autocast: no bf16 rounding).  g fp32 dense [rows][C]. */
+int mmpt_layerscale_bwd(int64_t rows, int64_t C, const float* g, const float* gamma,
+                        const void* y, int64_t ld_y, void* dy, int64_t ld_dy, float* dgamma,
+                        void* workspace, void* stream);
+int64_t mmpt_ln16_bwd_workspace_bytes(int64_t rows, int64_t h);
+/* The backward of mmpt_mlm_ln_fwd (a LayerNorm that reads a bf16 activation c and feeds a GEMM):
+ *   dc  = bf16(LN'(f32(dn16); f32(c), mean, rstd, w))   bf16 [rows][ld_dc]
+ *   dw += Σ_rows dn · x̂,  db += Σ_rows dn               fp32 (nullable)
+ * mmpt_mlm_ln_bwd without the dGELU and dsum. */
+int mmpt_ln16_bwd(int64_t rows, int64_t h, const void* c, int64_t ld_c, const float* mean,
+                  const float* rstd, const float* w, const void* dn16, int64_t ld_dn16, void* dc,
+                  int64_t ld_dc, float* dw, float* db, void* workspace, void* stream);
+/* p[b][c] = (Σ_hw x[b][hw][c]) / HW in fp32; x fp32 [B][HW][C], p fp32 [B][C]; B <= 65535.  Here
+ * and in the backward the division is torch's device arithmetic for a division by a scalar: one
+ * multiplication by the fp32 reciprocal float(1) / float(HW). */
+int mmpt_avgpool_fwd(int64_t B, int64_t HW, int64_t C, const float* x, float* p, void* stream);
+/* dx[b][hw][c] = dp[b][c] / HW: every row of dx is written, no memset beside it. */
+int mmpt_avgpool_bwd(int64_t B, int64_t HW, int64_t C, const float* dp, float* dx, void* stream);
+/* The 2x2/s2 downsample conv as a GEMM: rows[(b, oy, ox)][(ky*2 + kx)*C + c] =
+ * x[b][2 oy + ky][2 ox + kx][c]; x bf16 [B][H][W][C] (H, W even), rows bf16 [B*H/2*W/2][4C]. */
+int mmpt_patchify2_nhwc(int64_t B, int64_t H, int64_t W, int64_t C, const void* x, void* rows,
+                        void* stream);
+/* The inverse permutation, widened to fp32 (exact): dx fp32 [B][H][W][C] from bf16 rows. */
+int mmpt_unpatchify2_nhwc(int64_t B, int64_t H, int64_t W, int64_t C, const void* rows, float* dx,
+                          void* stream);
+
+/* ------------------------------------------------------------------------
  * ZeRO++ quantized communication (sharding = "zero_3++"): replaces DeepSpeed's
  * `zero_quantized_weights` / `zero_quantized_gradients` kernels that
  * src/train.py:196-201 switches on.  Blockwise symmetric quantization, 256-element

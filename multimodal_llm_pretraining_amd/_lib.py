@@ -115,6 +115,19 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_mlm_ln_fwd": (I32, [I64, I64, F32, P, I64, P, P, P, I64, P, P, P]),
     "mmpt_mlm_ln_bwd_workspace_bytes": (I64, [I64, I64]),
     "mmpt_mlm_ln_bwd": (I32, [I64, I64, P, I64, P, P, P, P, I64, P, I64, P, I64, P, P, P, P, P]),
+    "mmpt_dwconv7_fwd": (I32, [I64, I64, I64, I64, P, P, P, P, P]),
+    "mmpt_dwconv7_bwd_input": (I32, [I64, I64, I64, I64, P, P, P, P, P]),
+    "mmpt_dwconv7_bwd_weight_workspace_bytes": (I64, [I64, I64, I64, I64]),
+    "mmpt_dwconv7_bwd_weight": (I32, [I64, I64, I64, I64, P, P, P, P, P, P]),
+    "mmpt_layerscale_add_fwd": (I32, [I64, I64, P, P, P, I64, P, P]),
+    "mmpt_layerscale_bwd_workspace_bytes": (I64, [I64, I64]),
+    "mmpt_layerscale_bwd": (I32, [I64, I64, P, P, P, I64, P, I64, P, P, P]),
+    "mmpt_ln16_bwd_workspace_bytes": (I64, [I64, I64]),
+    "mmpt_ln16_bwd": (I32, [I64, I64, P, I64, P, P, P, P, I64, P, I64, P, P, P, P]),
+    "mmpt_avgpool_fwd": (I32, [I64, I64, I64, P, P, P]),
+    "mmpt_avgpool_bwd": (I32, [I64, I64, I64, P, P, P]),
+    "mmpt_patchify2_nhwc": (I32, [I64, I64, I64, I64, P, P, P]),
+    "mmpt_unpatchify2_nhwc": (I32, [I64, I64, I64, I64, P, P, P]),
 }
 
 

@@ -162,10 +162,47 @@ class TextConfig:
 
 
 @dataclass(frozen=True)
+class ConvNextConfig:
+    """ConvNeXt (tf:models/convnext): a 4x4/s4 patch stem + LayerNorm, four stages of
+    ConvNextLayer blocks (7x7 depthwise conv, LayerNorm, 4x pointwise MLP with erf-GELU, layer
+    scale gamma, residual) with a LayerNorm + 2x2/s2 conv downsample in front of stages 1-3,
+    then the global average pool, a LayerNorm (head_eps = ConvNextConfig.layer_norm_eps) and the
+    classifier.  drop_path_rate is 0 in every configuration the reference builds."""
+
+    hidden_sizes: tuple = (96, 192, 384, 768)
+    depths: tuple = (3, 3, 9, 3)
+    image: int = 224
+    patch: int = 4
+    channels: int = 3
+    eps: float = 1e-6
+    head_eps: float = 1e-12
+    layer_scale_init: float = 1e-6
+
+    def __post_init__(self):
+        if len(self.hidden_sizes) != 4 or len(self.depths) != 4:
+            raise ValueError("ConvNextConfig: four stages (hidden_sizes and depths of length 4)")
+        if any(c <= 0 or c % 8 for c in self.hidden_sizes) or any(d <= 0 for d in self.depths):
+            raise ValueError("ConvNextConfig: hidden_sizes positive multiples of 8, depths >= 1")
+        if self.image % (self.patch * 8):
+            raise ValueError("ConvNextConfig: image must be a multiple of 8 * patch (three 2x2 "
+                             "downsamples after the stem)")
+
+    @property
+    def patch_k(self) -> int:
+        """im2col width C·p·p padded to a multiple of 8 (16-B GEMM rows; zero columns)."""
+        return (self.channels * self.patch * self.patch + 7) // 8 * 8
+
+    def side(self, stage: int) -> int:
+        """H = W of a stage's plane."""
+        return self.image // self.patch >> stage
+
+
+@dataclass(frozen=True)
 class ModelConfig:
     """text + optional vision tower: a language model or a LLaVA composition.  text = None
-    with num_classes > 0: a vision-only classifier (ViTForImageClassification,
-    tf:models/vit/modeling_vit.py: the encoder, vit.layernorm, the CLS row, a Linear head)."""
+    with num_classes > 0: a vision-only classifier — ViTForImageClassification
+    (tf:models/vit/modeling_vit.py: the encoder, vit.layernorm, the CLS row, a Linear head) over
+    `vision`, or ConvNextForImageClassification over `convnext`."""
 
     text: TextConfig | None = None
     vision: VisionConfig | None = None
@@ -175,9 +212,16 @@ class ModelConfig:
     # lm_head) are frozen — only the projector is trained.
     freeze_tower_and_llm: bool = False
     num_classes: int = 0  # > 0 (with text = None): the classification head's labels
+    convnext: ConvNextConfig | None = None
 
     def __post_init__(self):
-        if self.text is None:
+        if self.convnext is not None:
+            if self.text is not None or self.vision is not None or self.num_classes <= 0:
+                raise ValueError("a ConvNeXt model is a vision-only classifier: no text model, no "
+                                 "ViT tower, num_classes > 0")
+            if self.freeze_tower_and_llm:
+                raise ValueError("the ConvNeXt classifier has nothing frozen")
+        elif self.text is None:
             if self.vision is None or self.num_classes <= 0:
                 raise ValueError("a model without a text model is a vision-only classifier: it "
                                  "needs a vision tower and num_classes > 0")
@@ -274,6 +318,17 @@ PRESETS["tiny-vit-cls"] = ModelConfig(
                         feature_layer=-1), num_classes=1001)
 PRESETS["tiny-vit-cls-drop"] = ModelConfig(
     vision=replace(PRESETS["tiny-vit-cls"].vision, hidden_dropout=0.1), num_classes=1001)
+# the reference's convnext-* (src/models/convnext.py: ConvNeXt-L / -XL at 224 px, ImageNet-1k or
+# -22k labels) and a tiny form for the parity tests: planes 16, 8, 4, 2 (two smaller than the 7x7
+# filter), channel counts that are no powers of two, a stage of three blocks
+CONVNEXT_L = ConvNextConfig(hidden_sizes=(192, 384, 768, 1536), depths=(3, 3, 27, 3))
+CONVNEXT_XL = ConvNextConfig(hidden_sizes=(256, 512, 1024, 2048), depths=(3, 3, 27, 3))
+PRESETS["convnext-large-1k"] = ModelConfig(convnext=CONVNEXT_L, num_classes=1000)
+PRESETS["convnext-large-22k"] = ModelConfig(convnext=CONVNEXT_L, num_classes=21841)
+PRESETS["convnext-xlarge-22k"] = ModelConfig(convnext=CONVNEXT_XL, num_classes=21841)
+PRESETS["tiny-convnext"] = ModelConfig(
+    convnext=ConvNextConfig(hidden_sizes=(24, 48, 96, 192), depths=(1, 1, 3, 1), image=64),
+    num_classes=1001)
 PRESETS["tiny-lm"] = ModelConfig(text=TextConfig(hidden=256, layers=2, heads=2, ffn=512, vocab=512))
 # Pythia-2.8B's head shape (head_dim 80 -> padded D = 128 attention, 20 rotary dims)
 PRESETS["tiny-lm-d80"] = ModelConfig(text=TextConfig(hidden=320, layers=2, heads=4, ffn=640,
@@ -364,6 +419,36 @@ def param_shapes(cfg: ModelConfig) -> dict[str, tuple[int, ...]]:
     """The build's flat state-dict layout (HF mapping: oracle/hf_mapping.py)."""
     s: dict[str, tuple[int, ...]] = {}
     t = cfg.text
+    if cfg.convnext is not None:
+        cn = cfg.convnext
+        s["convnext.stem.weight"] = (cn.hidden_sizes[0], cn.patch_k)
+        s["convnext.stem.bias"] = (cn.hidden_sizes[0],)
+        s["convnext.stem_ln.weight"] = (cn.hidden_sizes[0],)
+        s["convnext.stem_ln.bias"] = (cn.hidden_sizes[0],)
+        for si, (C, depth) in enumerate(zip(cn.hidden_sizes, cn.depths)):
+            p = f"convnext.stages.{si}."
+            if si > 0:
+                Cin = cn.hidden_sizes[si - 1]
+                s[p + "down_ln.weight"] = (Cin,)
+                s[p + "down_ln.bias"] = (Cin,)
+                s[p + "down.weight"] = (C, 4 * Cin)  # columns (ky, kx, c)
+                s[p + "down.bias"] = (C,)
+            for j in range(depth):
+                q = f"{p}layers.{j}."
+                s[q + "dw.weight"] = (49, C)             # tap-major (HF: [C, 1, 7, 7])
+                s[q + "dw.bias"] = (C,)
+                s[q + "ln.weight"] = (C,)
+                s[q + "ln.bias"] = (C,)
+                s[q + "fc1.weight"] = (4 * C, C)         # pwconv1
+                s[q + "fc1.bias"] = (4 * C,)
+                s[q + "fc2.weight"] = (C, 4 * C)         # pwconv2
+                s[q + "fc2.bias"] = (C,)
+                s[q + "gamma"] = (C,)                    # layer_scale_parameter
+        s["convnext.ln_post.weight"] = (cn.hidden_sizes[-1],)
+        s["convnext.ln_post.bias"] = (cn.hidden_sizes[-1],)
+        s["cls_head.weight"] = (cfg.classes_padded, cn.hidden_sizes[-1])
+        s["cls_head.bias"] = (cfg.classes_padded,)
+        return s
     if cfg.vision is not None:
         v = cfg.vision
         s["vision.patch.weight"] = (v.hidden, v.patch_k)
@@ -467,9 +552,32 @@ def num_params(cfg: ModelConfig) -> int:
     return n
 
 
+def _convnext_flops(cfg: ModelConfig, executed: bool = False) -> float:
+    """What FlopCounterMode (the reference's counter, src/benchmarking/flops.py) reports for one
+    forward + backward of ConvNextForImageClassification, per sample.  Convolutions and Linears
+    count 2·MACs forward and once more for each gradient; the stem has no input gradient (pixels
+    need none).  The counter's formula for a convolution's weight gradient multiplies the output
+    channels by the batch-transposed input channels, so for the depthwise conv (groups = C) it
+    reports C times the MACs executed: restated here as the counter has it.  `executed`: that
+    gradient at the 2·MACs it takes (the count behind `executed_mfu`)."""
+    cn = cfg.convnext
+    hw = cn.side(0) ** 2
+    total = 2 * 2 * hw * cn.hidden_sizes[0] * cn.channels * cn.patch ** 2
+    for si, (C, depth) in enumerate(zip(cn.hidden_sizes, cn.depths)):
+        hw = cn.side(si) ** 2
+        if si > 0:
+            total += 3 * 2 * hw * C * 4 * cn.hidden_sizes[si - 1]
+        dw = 2 * hw * C * 49
+        total += depth * (2 * dw + dw * (1 if executed else C) + 3 * 2 * (2 * hw * C * 4 * C))
+    total += 3 * 2 * cn.hidden_sizes[-1] * cfg.num_classes
+    return float(total)
+
+
 def _classifier_flops(cfg: ModelConfig) -> float:
     """3 × (patch GEMM + every layer + the head's 2·hidden·num_classes): every layer is used
     and the attention is non-causal, so the executed count is the reference-convention one."""
+    if cfg.convnext is not None:
+        return _convnext_flops(cfg)
     v = cfg.vision
     Sv = v.num_patches + 1
     fwd = 2 * v.num_patches * v.hidden * v.channels * v.patch ** 2
@@ -527,6 +635,8 @@ def executed_flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     over the lower triangle with the diagonal (S(S+1)/2 score/PV pairs per head instead of
     S²), and only the vision layers the model reads (`used_layers`: vision_feature_layer
     -2 leaves the last one unbuilt).  Non-causal ViT attention stays square."""
+    if cfg.convnext is not None:
+        return _convnext_flops(cfg, executed=True)
     if cfg.classifier:
         return _classifier_flops(cfg)
     t = cfg.text

@@ -23,7 +23,7 @@ namespace {
 
 constexpr int PL_WAVES = 4;
 constexpr int PL_BLOCKS = 1024;
-enum { PL_ADD = 0, PL_EMB = 1, PL_MLM = 2 };
+enum { PL_ADD = 0, PL_EMB = 1, PL_MLM = 2, PL_LN16 = 3 };  // LN16: MLM's backward without the dGELU
 
 __device__ __forceinline__ float4 ld_bf16x4(const bf16_t* p) {
   const uint2 u = *(const uint2*)p;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
       o.y += rs * (g1[j].y - xh[j].y * c1a - c1b);
       o.z += rs * (g1[j].z - xh[j].z * c1a - c1b);
       o.w += rs * (g1[j].w - xh[j].w * c1a - c1b);
-      if (MODE != PL_MLM) ((float4*)(a.o32 + (long)row * h))[i] = o;
+      if (MODE != PL_MLM && MODE != PL_LN16) ((float4*)(a.o32 + (long)row * h))[i] = o;
       if (MODE == PL_EMB) {  // dtype[0] = Σ_rows de in fp32: these gradients are outside autocast
         aq[j].x += o.x; aq[j].y += o.y; aq[j].z += o.z; aq[j].w += o.w;
         continue;
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
           q.z = drop_bf_f(q.z, k.w[2] >= a.thr, a.scale);
           q.w = drop_bf_f(q.w, k.w[3] >= a.thr, a.scale);
         }
-      } else {  // dpre = bf16(dg * gelu'(pre)): the BF16_DGELU epilogue's arithmetic
+      } else if (MODE == PL_MLM) {  // dpre = bf16(dg * gelu'(pre)): the BF16_DGELU epilogue's arithmetic
         const float4 pv = ld_bf16x4(a.pre + (long)row * a.ld_pre + i * 4);
         q.x = round_bf(q.x * gelu_grad_f(pv.x));
         q.y = round_bf(q.y * gelu_grad_f(pv.y));
@@ -512,4 +512,28 @@ extern "C" int mmpt_mlm_ln_bwd(int64_t rows, int64_t h, const void* g, int64_t l
   a.o16 = (bf16_t*)dpre; a.ld_o16 = ld_dpre;
   a.partials = (float*)workspace; a.want_q2 = dsum != nullptr;
   return launch_bwd<PL_MLM>(a, dw, db, dsum, nullptr, 1, (hipStream_t)stream, "mlm_ln_bwd");
+}
+
+extern "C" int64_t mmpt_ln16_bwd_workspace_bytes(int64_t rows, int64_t h) {
+  return mmpt_add_layernorm_bwd_workspace_bytes(rows, h);
+}
+
+extern "C" int mmpt_ln16_bwd(int64_t rows, int64_t h, const void* c, int64_t ld_c,
+                             const float* mean, const float* rstd, const float* w,
+                             const void* dn16, int64_t ld_dn16, void* dc, int64_t ld_dc, float* dw,
+                             float* db, void* workspace, void* stream) {
+  MMPT_PL_SHAPE("ln16_bwd");
+  MMPT_PL_LD("ln16_bwd", ld_c);
+  MMPT_PL_LD("ln16_bwd", ld_dn16);
+  MMPT_PL_LD("ln16_bwd", ld_dc);
+  MMPT_REQUIRE(c && mean && rstd && w && dn16 && dc && workspace, "ln16_bwd: null pointer");
+  MMPT_REQUIRE(al16(c) && al16(w) && al16(dn16) && al16(dc) && al16(workspace),
+               "ln16_bwd: pointers must be 16-byte aligned");
+  PlArgs a = {};
+  a.rows = (int)rows; a.h = (int)h; a.w = w; a.mean_in = mean; a.rstd_in = rstd;
+  a.x16 = (const bf16_t*)c; a.ld_x16 = ld_c;
+  a.dy16 = (const bf16_t*)dn16; a.ld_dy16 = ld_dn16;
+  a.o16 = (bf16_t*)dc; a.ld_o16 = ld_dc;
+  a.partials = (float*)workspace;
+  return launch_bwd<PL_LN16>(a, dw, db, nullptr, nullptr, 0, (hipStream_t)stream, "ln16_bwd");
 }

@@ -24,6 +24,12 @@ _cls_backward).
 A masked LM (TextConfig.arch "roberta": RobertaForMaskedLM, tf:models/roberta/modeling_roberta.py)
 is a post-LN encoder: LayerNorm after each residual add (include/mmpt.h K20), learned positions,
 the MLM head on the labelled rows (_roberta_forward / _roberta_backward).
+
+A ConvNeXt classifier (ModelConfig.convnext: ConvNextForImageClassification,
+tf:models/convnext/modeling_convnext.py) keeps its activations channels-last: rows (b, y, x),
+columns c.  The 7x7 depthwise conv, the layer-scale residual, the pool and the 2x2 patch
+permutations are include/mmpt.h K21; every 1x1 conv, the 4x4 stem and the 2x2 downsample are
+GEMMs over those rows (_convnext_forward / _convnext_backward).
 """
 
 from __future__ import annotations
@@ -175,7 +181,7 @@ class Batch:
             self._stage(cfg, input_ids, labels, pixel_values, device, mask)
 
     def _init_images(self, cfg, input_ids, labels, pixel_values, device, stream, attention_mask):
-        v = cfg.vision
+        v = cfg.vision if cfg.convnext is None else cfg.convnext
         if input_ids is not None or attention_mask is not None:
             raise ValueError("an image classifier takes pixel_values and labels, not input_ids / "
                              "attention_mask")
@@ -185,7 +191,9 @@ class Batch:
         if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != want:
             raise ValueError(f"pixel_values shape {tuple(pixel_values.shape)} != [B, "
                              f"{v.channels}, {v.image}, {v.image}]")
-        self.B, self.S = pixel_values.shape[0], v.num_patches + 1
+        # S / T count the rows of the first residual stream: ViT tokens, or ConvNeXt stem pixels
+        self.B = pixel_values.shape[0]
+        self.S = v.num_patches + 1 if cfg.convnext is None else v.side(0) ** 2
         if tuple(labels.shape) != (self.B,):
             raise ValueError(f"labels shape {tuple(labels.shape)} != [{self.B}] (one class per "
                              "image)")
@@ -467,7 +475,8 @@ class Engine:
         self.frozen = cfg.freeze_tower_and_llm
         store.transposed = [n for n in store.shapes if len(store.shapes[n]) == 2 and
                             n not in ("vision.patch.weight", "text.embed", "vision.pos",
-                                      "text.pos_embed", "text.type_embed")]
+                                      "text.pos_embed", "text.type_embed",
+                                      "convnext.stem.weight") and not n.endswith(".dw.weight")]
         if tied:  # the tied lm_head's input gradient reads E^T
             store.transposed.append("text.embed")
         if self.frozen and not t.llama:
@@ -559,6 +568,8 @@ class Engine:
         cfg = self.cfg
         f32 = getattr(self.s, "fp32_units", ())
         order = []
+        if cfg.convnext is not None:  # one unit per ConvNextStage, the stem and the head
+            return ["convnext.stem"] + [f"convnext.stages.{s}" for s in range(4)] + ["cls_head"]
         if cfg.multimodal:
             order += ["vision.patch"] + (["vision.pos"] if "vision.pos" in f32 else [])
             order += [f"vision.layers.{i}" for i in range(cfg.vision.used_layers)]
@@ -1180,6 +1191,189 @@ class Engine:
         self._join_side()
         self.cache.clear()
 
+    # -------------------------------------------------------------- ConvNeXt
+    # The residual stream x is fp32 [B·H·W, C], channels-last.  A block keeps (x, c, mean, rstd,
+    # n, pre, act, y) for its backward; with activation checkpointing a STAGE keeps only its
+    # input and is recomputed before its backward (the reference's
+    # ConvNextEncoderWithCheckpointing wraps each ConvNextStage).
+    def _cn_f32_of_bf16(self, x, name):
+        """f32(bf16(x·Wᵀ + b)): a conv output (bf16 under autocast) held exactly in the fp32
+        stream — the residual epilogue over a zero residual."""
+        W = self.s.w(name + ".weight")
+        zero = torch.zeros(x.shape[0], W.shape[0], dtype=F32, device=self.dev)
+        return self._linear(x, name, epi=K.EPI_F32_RESID, out2=zero)
+
+    def _cn_block_fwd(self, p, x, B, side):
+        """ConvNextLayer under autocast: x + gamma * f32(fc2(gelu(fc1(LN(dwconv(bf16 x))))))."""
+        R, C = x.shape
+        eps = self.cfg.convnext.eps
+        c = self._e(R, C)
+        K.dwconv7_fwd(x.view(B, side, side, C), self.s.w(p + "dw.weight"), self.s.w(p + "dw.bias"),
+                      c.view(B, side, side, C))
+        n = self._e(R, C)
+        m, r = self._e(R, dtype=F32), self._e(R, dtype=F32)
+        K.mlm_ln_fwd(c, self.s.p(p + "ln.weight"), self.s.p(p + "ln.bias"), eps, n, m, r)
+        pre, act = self._e(R, 4 * C), self._e(R, 4 * C)
+        self._linear(n, p + "fc1", out=pre, epi=K.EPI_BF16_GELU, out2=act)
+        y = self._linear(act, p + "fc2")
+        xn = self._e(R, C, dtype=F32)
+        K.layerscale_add_fwd(x, self.s.p(p + "gamma"), y, xn)
+        return xn, (x, c, m, r, n, pre, act, y)
+
+    def _cn_block_bwd(self, p, g, saved, B, side):
+        """g: the fp32 gradient of the block's output, overwritten by its input's."""
+        x, c, m, r, n, pre, act, y = saved
+        R, C = x.shape
+        self._side_fence()
+        dy = self._e(R, C)
+        K.layerscale_bwd(g, self.s.p(p + "gamma"), y, dy, self.s.g(p + "gamma"))
+        dpre = self._dx_dgelu(dy, p + "fc2", pre, bias_of=p + "fc1")
+        self._dw(dy, act, p + "fc2")
+        dn = self._dx(dpre, p + "fc1")
+        self._dw(dpre, n, p + "fc1", bias=False)
+        dc = self._e(R, C)
+        K.ln16_bwd(c, m, r, self.s.p(p + "ln.weight"), dn, dc, dw=self.s.g(p + "ln.weight"),
+                   db=self.s.g(p + "ln.bias"))
+        dc4 = dc.view(B, side, side, C)
+        K.dwconv7_bwd_weight(x.view(B, side, side, C), dc4, self.s.g(p + "dw.weight"),
+                             self.s.g(p + "dw.bias"))
+        g4 = g.view(B, side, side, C)
+        K.dwconv7_bwd_input(dc4, self.s.w(p + "dw.weight"), g4, dx_in=g4)
+        return g
+
+    def _cn_stage_fwd(self, s, x, B, _S=None):
+        """ConvNextStage s: LayerNorm + 2x2/s2 conv (s >= 1), then its blocks."""
+        cn = self.cfg.convnext
+        C, side = cn.hidden_sizes[s], cn.side(s)
+        p = f"convnext.stages.{s}."
+        ckpt = self.checkpointing and not self._recomputing
+        x_in, down = x, None
+        if s > 0:
+            Cin, sin = cn.hidden_sizes[s - 1], cn.side(s - 1)
+            yln = self._e(x.shape[0], Cin)
+            m, r = self._e(x.shape[0], dtype=F32), self._e(x.shape[0], dtype=F32)
+            K.layernorm_fwd(x, self.s.p(p + "down_ln.weight"), self.s.p(p + "down_ln.bias"), cn.eps,
+                            yln, m, r)
+            rows = self._e(B * side * side, 4 * Cin)
+            K.patchify2_nhwc(yln.view(B, sin, sin, Cin), rows)
+            down = (x, m, r, rows)
+            x = self._cn_f32_of_bf16(rows, p + "down")
+        blocks = []
+        for j in range(cn.depths[s]):
+            x, saved = self._cn_block_fwd(f"{p}layers.{j}.", x, B, side)
+            blocks.append(saved)
+        if ckpt:
+            self.cache[("cn", s)] = ("ckpt", x_in)
+        else:
+            self.cache[("cn", s)] = (down, blocks)
+        return x
+
+    def _cn_stage_bwd(self, s, g, B):
+        cn = self.cfg.convnext
+        C, side = cn.hidden_sizes[s], cn.side(s)
+        p = f"convnext.stages.{s}."
+        self._unit_bwd(f"convnext.stages.{s}")
+        self._restore(("cn", s), self._cn_stage_fwd, s, B, None)
+        down, blocks = self.cache.pop(("cn", s))
+        for j in reversed(range(cn.depths[s])):
+            g = self._cn_block_bwd(f"{p}layers.{j}.", g, blocks.pop(), B, side)
+        if down is not None:
+            x, m, r, rows = down
+            Cin, sin = cn.hidden_sizes[s - 1], cn.side(s - 1)
+            dq = self._e(g.shape[0], C)  # the stage-entry gradient, rounded to bf16 once
+            K.cast_f32_bf16(g, dq)
+            drows = self._dx(dq, p + "down")
+            self._dw(dq, rows, p + "down")
+            dyln = self._e(x.shape[0], Cin, dtype=F32)
+            K.unpatchify2_nhwc(drows, dyln.view(B, sin, sin, Cin))
+            g = self._e(x.shape[0], Cin, dtype=F32)
+            K.layernorm_f32_bwd(x, m, r, dyln, self.s.p(p + "down_ln.weight"), g,
+                                self.s.g(p + "down_ln.weight"), self.s.g(p + "down_ln.bias"))
+        self._unit_done(f"convnext.stages.{s}")
+        self._ready((p,))
+        return g
+
+    def _convnext_forward(self, batch: Batch, grad_scale: float, need_grad: bool) -> torch.Tensor:
+        """ConvNextForImageClassification: 4x4/s4 stem + LayerNorm, the four stages, the global
+        average pool, LayerNorm (head_eps), the classifier with its bias, Σ_images CE."""
+        cfg, cn = self.cfg, self.cfg.convnext
+        B, C0, C3 = batch.B, cn.hidden_sizes[0], cn.hidden_sizes[-1]
+        self._vl = None
+        if self.dev.type == "cuda":
+            batch.use(torch.cuda.current_stream(self.dev))
+        region = getattr(self.units, "region", None)
+        if region is not None:
+            region()
+        self._drop_begin(need_grad)
+        R0 = B * cn.side(0) ** 2
+        cols = self._e(R0, cn.patch_k)
+        K.im2col(batch.pixels, cn.patch, cols)
+        self._unit_fwd("convnext.stem")
+        po = self._cn_f32_of_bf16(cols, "convnext.stem")
+        x = self._e(R0, C0, dtype=F32)
+        m0, r0 = self._e(R0, dtype=F32), self._e(R0, dtype=F32)
+        K.layernorm_f32_fwd(po, self.s.p("convnext.stem_ln.weight"),
+                            self.s.p("convnext.stem_ln.bias"), cn.eps, x, m0, r0)
+        for s in range(4):
+            self._unit_fwd(f"convnext.stages.{s}")
+            x = self._cn_stage_fwd(s, x, B)
+        HW = cn.side(3) ** 2
+        pooled = self._e(B, C3, dtype=F32)
+        K.avgpool_fwd(x.view(B, HW, C3), pooled)
+        y = self._e(B, C3)
+        m, r = self._e(B, dtype=F32), self._e(B, dtype=F32)
+        K.layernorm_fwd(pooled, self.s.p("convnext.ln_post.weight"),
+                        self.s.p("convnext.ln_post.bias"), cn.head_eps, y, m, r)
+        self._unit_fwd("cls_head")
+        logits = self._linear(y, "cls_head")
+        loss_rows = self._e(B, dtype=F32)
+        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
+                        logits if need_grad else None, vocab_valid=cfg.num_classes)
+        loss = self._e(1, dtype=F32)
+        K.sum_f32(loss_rows, loss)
+        if need_grad:
+            self.cache["head"] = (pooled, m, r, y, logits)
+            self.cache["stem"] = (cols, po, m0, r0)
+        else:
+            self.cache.clear()
+        return loss
+
+    def _convnext_backward(self, batch: Batch, scale: torch.Tensor | None) -> None:
+        cn = self.cfg.convnext
+        B, C0, C3 = batch.B, cn.hidden_sizes[0], cn.hidden_sizes[-1]
+        self._vl = None
+        pooled, m, r, y, dlogits = self.cache.pop("head")
+        cols, po, m0, r0 = self.cache.pop("stem")
+        if scale is not None:
+            dlogits.mul_(scale.to(torch.float32))
+        self._unit_bwd("cls_head")
+        dy = self._dx(dlogits, "cls_head")
+        self._dw(dlogits, y, "cls_head")  # + the classifier's bias gradient
+        self._unit_done("cls_head")
+        del dlogits
+        dp = self._e(B, C3, dtype=F32)
+        K.layernorm_bwd(pooled, m, r, dy, self.s.p("convnext.ln_post.weight"), dp,
+                        self.s.g("convnext.ln_post.weight"), self.s.g("convnext.ln_post.bias"))
+        HW = cn.side(3) ** 2
+        g = self._e(B * HW, C3, dtype=F32)
+        K.avgpool_bwd(dp, g.view(B, HW, C3))
+        self._ready(("cls_head.", "convnext.ln_post."))
+        for s in reversed(range(4)):
+            g = self._cn_stage_bwd(s, g, B)
+        # the stem: its LayerNorm read the bf16 conv output, whose gradient is bf16
+        self._side_fence()
+        self._unit_bwd("convnext.stem")
+        dpo = torch.empty_like(g)
+        K.layernorm_f32_bwd(po, m0, r0, g, self.s.p("convnext.stem_ln.weight"), dpo,
+                            self.s.g("convnext.stem_ln.weight"), self.s.g("convnext.stem_ln.bias"))
+        dpb = self._e(g.shape[0], C0)
+        K.cast_f32_bf16(dpo, dpb)
+        self._dw(dpb, cols, "convnext.stem")
+        self._unit_done("convnext.stem")
+        self._ready(("convnext.stem.", "convnext.stem_ln."))
+        self._join_side()
+        self.cache.clear()
+
     # -------------------------------------------------------------- RoBERTa (post-LN encoder)
     # The stream between sub-layers is fp32 AND normalised: each sub-layer ends in
     # LayerNorm(dropout(branch) + input) (include/mmpt.h K20).  A layer's input is the pair
@@ -1374,6 +1568,8 @@ class Engine:
     def forward(self, batch: Batch, grad_scale: float, need_grad: bool = True) -> torch.Tensor:
         """Returns Σ_tokens CE (device fp32 [1]); when need_grad, dlogits are written
         (scaled by grad_scale = 1/num_items of the global batch) and the caches kept."""
+        if self.cfg.convnext is not None:
+            return self._convnext_forward(batch, grad_scale, need_grad)
         if self.cfg.classifier:
             return self._cls_forward(batch, grad_scale, need_grad)
         if self.cfg.text.roberta:
@@ -1429,6 +1625,8 @@ class Engine:
     def backward(self, batch: Batch, scale: torch.Tensor | None = None) -> None:
         """Accumulates every parameter gradient into the flat grad buffer.  `scale`
         (device scalar, e.g. autograd's grad_output) multiplies the loss gradient."""
+        if self.cfg.convnext is not None:
+            return self._convnext_backward(batch, scale)
         if self.cfg.classifier:
             return self._cls_backward(batch, scale)
         if self.cfg.text.roberta:

@@ -873,3 +873,119 @@ def mlm_ln_bwd(g, mean, rstd, w, dn16, pre, dpre, dw=None, db=None, dsum=None) -
     _lib.call("mmpt_mlm_ln_bwd", rows, h, g.data_ptr(), ld_g, mean.data_ptr(), rstd.data_ptr(),
               w.data_ptr(), dn16.data_ptr(), ld_dn, pre.data_ptr(), ld_pre, dpre.data_ptr(), ld_dp,
               _p(dw), _p(db), _p(dsum), ws.data_ptr(), _stream())
+
+
+# ----------------------------------------------------------------------------- ConvNeXt (K21)
+# NHWC activations as 4-D dense tensors [B, H, W, C]; depthwise weights tap-major [49, C].
+def _nhwc(t, dtype, name, shape=None):
+    _check(t, dtype, name)
+    if t.dim() != 4 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name}: expected a dense NHWC tensor{'' if shape is None else ' ' + str(tuple(shape))}, "
+                         f"got {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+def dwconv7_fwd(x, w, bias, c) -> None:
+    """c = bf16(dwconv7x7(bf16(x); w, bias)), padding 3; x fp32 / c bf16 NHWC, w bf16 [49, C]."""
+    B, H, W, C = _nhwc(x, torch.float32, "dwconv7_fwd.x")
+    _nhwc(c, torch.bfloat16, "dwconv7_fwd.c", (B, H, W, C))
+    _dense(w, torch.bfloat16, (49, C), "dwconv7_fwd.w")
+    _dense(bias, torch.bfloat16, (C,), "dwconv7_fwd.bias")
+    _lib.call("mmpt_dwconv7_fwd", B, H, W, C, x.data_ptr(), w.data_ptr(), bias.data_ptr(),
+              c.data_ptr(), _stream())
+
+
+def dwconv7_bwd_input(dc, w, dx_out, dx_in=None) -> None:
+    """dx_out = dx_in + f32(bf16(dwconv7x7^T(dc; w))); dx_in None = zero, may be dx_out."""
+    B, H, W, C = _nhwc(dc, torch.bfloat16, "dwconv7_bwd_input.dc")
+    _nhwc(dx_out, torch.float32, "dwconv7_bwd_input.dx_out", (B, H, W, C))
+    if dx_in is not None:
+        _nhwc(dx_in, torch.float32, "dwconv7_bwd_input.dx_in", (B, H, W, C))
+    _dense(w, torch.bfloat16, (49, C), "dwconv7_bwd_input.w")
+    _lib.call("mmpt_dwconv7_bwd_input", B, H, W, C, dc.data_ptr(), w.data_ptr(), _p(dx_in),
+              dx_out.data_ptr(), _stream())
+
+
+def dwconv7_bwd_weight(x, dc, dw, db) -> None:
+    """dw [49, C] += bf16(Σ dc * bf16(x) shifted), db [C] += bf16(Σ dc): fp32 gradients."""
+    B, H, W, C = _nhwc(x, torch.float32, "dwconv7_bwd_weight.x")
+    _nhwc(dc, torch.bfloat16, "dwconv7_bwd_weight.dc", (B, H, W, C))
+    _dense(dw, torch.float32, (49, C), "dwconv7_bwd_weight.dw")
+    _dense(db, torch.float32, (C,), "dwconv7_bwd_weight.db")
+    ws = workspace(_lib.query("mmpt_dwconv7_bwd_weight_workspace_bytes", B, H, W, C), slot=2)
+    _lib.call("mmpt_dwconv7_bwd_weight", B, H, W, C, x.data_ptr(), dc.data_ptr(), dw.data_ptr(),
+              db.data_ptr(), ws.data_ptr(), _stream())
+
+
+def layerscale_add_fwd(resid, gamma, y, out) -> None:
+    """out = resid + gamma * f32(y), two fp32 roundings; out may be resid."""
+    rows, C = resid.shape
+    _dense(resid, torch.float32, (rows, C), "layerscale_add_fwd.resid")
+    _dense(out, torch.float32, (rows, C), "layerscale_add_fwd.out")
+    _dense(gamma, torch.float32, (C,), "layerscale_add_fwd.gamma")
+    ld_y = _rows_bf16(y, rows, C, "layerscale_add_fwd.y")
+    _lib.call("mmpt_layerscale_add_fwd", rows, C, resid.data_ptr(), gamma.data_ptr(), y.data_ptr(),
+              ld_y, out.data_ptr(), _stream())
+
+
+def layerscale_bwd(g, gamma, y, dy, dgamma) -> None:
+    """dy = bf16(gamma * g); dgamma += Σ_rows g * f32(y)."""
+    rows, C = g.shape
+    _dense(g, torch.float32, (rows, C), "layerscale_bwd.g")
+    _dense(gamma, torch.float32, (C,), "layerscale_bwd.gamma")
+    _dense(dgamma, torch.float32, (C,), "layerscale_bwd.dgamma")
+    ld_y = _rows_bf16(y, rows, C, "layerscale_bwd.y")
+    ld_dy = _rows_bf16(dy, rows, C, "layerscale_bwd.dy")
+    ws = workspace(_lib.query("mmpt_layerscale_bwd_workspace_bytes", rows, C), slot=2)
+    _lib.call("mmpt_layerscale_bwd", rows, C, g.data_ptr(), gamma.data_ptr(), y.data_ptr(), ld_y,
+              dy.data_ptr(), ld_dy, dgamma.data_ptr(), ws.data_ptr(), _stream())
+
+
+def ln16_bwd(c, mean, rstd, w, dn16, dc, dw=None, db=None) -> None:
+    """dc = bf16(LN'(f32(dn16); f32(c))): the backward of mlm_ln_fwd; dw / db +=."""
+    rows, h = c.shape
+    ld_c = _rows_bf16(c, rows, h, "ln16_bwd.c")
+    ld_dn = _rows_bf16(dn16, rows, h, "ln16_bwd.dn16")
+    ld_dc = _rows_bf16(dc, rows, h, "ln16_bwd.dc")
+    ws = workspace(_lib.query("mmpt_ln16_bwd_workspace_bytes", rows, h), slot=2)
+    _lib.call("mmpt_ln16_bwd", rows, h, c.data_ptr(), ld_c, mean.data_ptr(), rstd.data_ptr(),
+              w.data_ptr(), dn16.data_ptr(), ld_dn, dc.data_ptr(), ld_dc, _p(dw), _p(db),
+              ws.data_ptr(), _stream())
+
+
+def avgpool_fwd(x, p) -> None:
+    """p [B, C] = mean over HW of x [B, HW, C] (fp32)."""
+    _check(x, torch.float32, "avgpool_fwd.x")
+    if x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("avgpool_fwd.x: expected a dense [B, HW, C] tensor")
+    B, HW, C = x.shape
+    _dense(p, torch.float32, (B, C), "avgpool_fwd.p")
+    _lib.call("mmpt_avgpool_fwd", B, HW, C, x.data_ptr(), p.data_ptr(), _stream())
+
+
+def avgpool_bwd(dp, dx) -> None:
+    """dx [B, HW, C] = dp [B, C] / HW on every row."""
+    _check(dx, torch.float32, "avgpool_bwd.dx")
+    if dx.dim() != 3 or not dx.is_contiguous():
+        raise ValueError("avgpool_bwd.dx: expected a dense [B, HW, C] tensor")
+    B, HW, C = dx.shape
+    _dense(dp, torch.float32, (B, C), "avgpool_bwd.dp")
+    _lib.call("mmpt_avgpool_bwd", B, HW, C, dp.data_ptr(), dx.data_ptr(), _stream())
+
+
+def patchify2_nhwc(x, rows) -> None:
+    """rows [B*H/2*W/2, 4C] (columns (ky, kx, c)) from x bf16 [B, H, W, C]."""
+    B, H, W, C = _nhwc(x, torch.bfloat16, "patchify2_nhwc.x")
+    if H % 2 or W % 2:
+        raise ValueError("patchify2_nhwc: H and W must be even")
+    _dense(rows, torch.bfloat16, (B * (H // 2) * (W // 2), 4 * C), "patchify2_nhwc.rows")
+    _lib.call("mmpt_patchify2_nhwc", B, H, W, C, x.data_ptr(), rows.data_ptr(), _stream())
+
+
+def unpatchify2_nhwc(rows, dx) -> None:
+    """dx fp32 [B, H, W, C] = the inverse permutation of bf16 rows [B*H/2*W/2, 4C]."""
+    B, H, W, C = _nhwc(dx, torch.float32, "unpatchify2_nhwc.dx")
+    if H % 2 or W % 2:
+        raise ValueError("unpatchify2_nhwc: H and W must be even")
+    _dense(rows, torch.bfloat16, (B * (H // 2) * (W // 2), 4 * C), "unpatchify2_nhwc.rows")
+    _lib.call("mmpt_unpatchify2_nhwc", B, H, W, C, rows.data_ptr(), dx.data_ptr(), _stream())

@@ -14,8 +14,10 @@ the LLaVA-pretrain recipe (src/models/llava.py:80-124) used for the C3 compositi
     configs (the reference's "naive" branch: eager attention); no fetch.
 `llava-pretrain` is the reference's own CLIP-L/14-336 + Llama-3.2-1B model (with its
 freeze); `vit` / `vit-bf16` its ViT-L/16 image classifier (src/models/vit.py); model types
-`roberta` / `roberta-bf16` its RoBERTa-large masked LM (src/models/roberta.py); model types
-outside the path (mamba, convnext, llava-finetune, vilt-*) raise.
+`roberta` / `roberta-bf16` its RoBERTa-large masked LM (src/models/roberta.py);
+`convnext-large-1k` / `convnext-large-22k` / `convnext-xlarge-22k` (and their `-bf16` forms) its
+ConvNeXt image classifiers (src/models/convnext.py); model types outside the path (mamba,
+llava-finetune, vilt-*) raise.
 """
 
 from __future__ import annotations
@@ -39,11 +41,13 @@ VitPythiaT = Literal["vit-b16-pythia-1b", "clip-l14-336-pythia-2.8b"]
 LlavaT = Literal["llava-pretrain", "llava-pretrain-unfrozen"]
 ViTT = Literal["vit", "vit-bf16"]
 RobertaT = Literal["roberta", "roberta-bf16"]
-ModelT = Literal[PythiaT, VitPythiaT, LlavaT, ViTT, RobertaT]
+ConvNextT = Literal["convnext-large-1k", "convnext-large-22k", "convnext-xlarge-22k",
+                    "convnext-large-1k-bf16", "convnext-large-22k-bf16",
+                    "convnext-xlarge-22k-bf16"]
+ModelT = Literal[PythiaT, VitPythiaT, LlavaT, ViTT, RobertaT, ConvNextT]
 # reference model types that are not on this path (out of scope;
 # llava-finetune needs a private checkpoint, src/models/llava.py:151)
-OUT_OF_SCOPE = ("mamba", "convnext-large-1k", "convnext-large-22k",
-                "convnext-xlarge-22k", "llava-finetune",
+OUT_OF_SCOPE = ("mamba", "llava-finetune",
                 "vilt-pretrain", "vilt-finetune", "vilt-original-pretrain",
                 "vilt-original-finetune")
 
@@ -295,6 +299,49 @@ class RobertaModelClass(BaseModelClass):
         return DummyTextModelingDataset(self.vocab_size, self.sequence_length, num_samples)
 
 
+class ConvNextModelClass(BaseModelClass):
+    """The reference's `convnext-*` (src/models/convnext.py:18-115): ConvNextForImageClassification
+    on the ConvNeXt-L / -XL 224-px configs with 1000 (ImageNet-1k) or 21,841 (ImageNet-22k)
+    labels; batch 4096, 93,600 steps (1k) or 311,940 (22k), fp32 (mixed_precision None), AdamW
+    lr 4e-3 β (0.9, 0.999) wd 0.05, cosine schedule with 312·20 (1k) or 3466·5 (22k) warmup
+    steps, no clipping, activation checkpointing per ConvNextStage.
+
+    The three reference names restate that recipe verbatim and, like `vit`, are faithful records
+    that TrainingClass.build_trainer refuses: this path has bf16-autocast kernels only.  The
+    `-bf16` names are the same models and recipes under bf16 autocast — the runnable variants."""
+
+    def build_model(self, use_custom_kernels: bool = True) -> nn.Module:
+        if use_custom_kernels:
+            return MMPTForPretraining(self.model_config)
+        return build_hf_model(self.model_config)
+
+    @property
+    def base_type(self) -> str:
+        return self.model_type.removesuffix("-bf16")
+
+    @property
+    def model_config(self) -> C.ModelConfig:
+        return C.get_config(self.base_type)
+
+    batch_size = property(lambda self: 4096)
+    training_steps = property(lambda self: 93600 if self.base_type == "convnext-large-1k"
+                              else 311940)
+    mixed_precision = property(lambda self: "bf16" if self.model_type.endswith("-bf16") else None)
+    optimizer = property(lambda self: torch.optim.AdamW)
+    optimizer_kwargs = property(lambda self: {"lr": 4e-3, "betas": (0.9, 0.999),
+                                              "weight_decay": 0.05})
+    scheduler_type = property(lambda self: "cosine")
+    scheduler_kwargs = property(lambda self: {
+        "num_warmup_steps": 312 * 20 if self.base_type == "convnext-large-1k" else 3466 * 5})
+    max_grad_norm = property(lambda self: 0.0)
+    fsdp_layers_to_wrap = property(lambda self: ["ConvNextStage"])
+    image_size = property(lambda self: 224)
+    num_classes = property(lambda self: 1000 if self.base_type == "convnext-large-1k" else 21841)
+
+    def load_dummy_dataset(self, num_samples: int = 20_000):
+        return DummyImageClassificationDataset(self.image_size, self.num_classes, num_samples)
+
+
 def get_model_class(model_type: str) -> BaseModelClass:
     """src/models/__init__.py:240-296 for the types on the MI355X path."""
     if model_type in PythiaModelClass._LR:
@@ -309,6 +356,8 @@ def get_model_class(model_type: str) -> BaseModelClass:
         return ViTModelClass(model_type)
     if model_type in ("roberta", "roberta-bf16"):
         return RobertaModelClass(model_type)
+    if model_type in ConvNextT.__args__:
+        return ConvNextModelClass(model_type)
     if model_type in OUT_OF_SCOPE:
         raise NotImplementedError(f"model type {model_type!r} is not on the MI355X hot path "
                                   "(SURVEY.md §8 scope)")
@@ -351,7 +400,8 @@ class MMPTForPretraining(nn.Module):
     labels, num_items_in_batch) → output with .loss; `.config.hidden_size` /
     `.config.text_config.hidden_size`; gradient_checkpointing_enable();
     for a vision-only classifier forward(pixel_values, labels [B]) and `.config.hidden_size` /
-    `.num_labels` / `.image_size`;
+    `.num_labels` / `.image_size` (a ConvNeXt: `.config.hidden_sizes` / `.depths` instead of
+    `.hidden_size`);
     parameters named like the flat store (state_dict keys = ParamStore names).
 
     Gradients live in the store's flat fp32 buffer; every `p.grad` is a view of it.
@@ -390,7 +440,14 @@ class MMPTForPretraining(nn.Module):
         self._grad_views = [self.store.g(n) for n in self.store.names()]
         self._attach_grads()
         t = cfg.text
-        if cfg.classifier:
+        if cfg.convnext is not None:
+            cn = cfg.convnext
+            self.config = SimpleNamespace(hidden_sizes=list(cn.hidden_sizes), depths=list(cn.depths),
+                                          num_stages=4, image_size=cn.image,
+                                          patch_size=cn.patch, num_channels=cn.channels,
+                                          num_labels=cfg.num_classes, use_cache=False,
+                                          model_type="mmpt")
+        elif cfg.classifier:
             v = cfg.vision
             self.config = SimpleNamespace(hidden_size=v.hidden, num_hidden_layers=v.layers,
                                           num_attention_heads=v.heads, intermediate_size=v.ffn,
@@ -414,8 +471,9 @@ class MMPTForPretraining(nn.Module):
 
     # -- HF-compatible knobs
     def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None):
-        """Per-layer activation checkpointing: each ViT / GPTNeoX layer keeps only its
-        input and recomputes its forward right before its backward (Engine.checkpointing)."""
+        """Per-layer activation checkpointing: each ViT / GPTNeoX layer (ConvNeXt: each stage)
+        keeps only its input and recomputes its forward right before its backward
+        (Engine.checkpointing)."""
         self.gradient_checkpointing = True
         self.engine.checkpointing = True
 
@@ -496,6 +554,17 @@ class MMPTForPretraining(nn.Module):
 def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
     """The reference's use_custom_kernels=False branch: plain transformers modules from
     explicit configs (eager attention), no hub access."""
+    if cfg.convnext is not None:
+        from transformers import ConvNextConfig, ConvNextForImageClassification
+
+        # facebook/convnext-{large,xlarge}-224(-22k)'s public hyper-parameters written out
+        cn = cfg.convnext
+        return ConvNextForImageClassification(ConvNextConfig(
+            num_channels=cn.channels, patch_size=cn.patch, num_stages=4,
+            hidden_sizes=list(cn.hidden_sizes), depths=list(cn.depths), hidden_act="gelu",
+            initializer_range=0.02, layer_norm_eps=cn.head_eps,
+            layer_scale_init_value=cn.layer_scale_init, drop_path_rate=0.0, image_size=cn.image,
+            num_labels=cfg.num_classes))
     if cfg.classifier:
         from transformers import ViTConfig, ViTForImageClassification
 

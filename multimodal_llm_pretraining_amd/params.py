@@ -25,7 +25,8 @@ def is_fp32_read(name: str) -> bool:
     contiguous region, so ZeRO can re-broadcast exactly that region after the update."""
     return name in ("text.embed", "vision.pos", "vision.cls", "text.pos_embed",
                     "text.type_embed") or ".ln" in name or "final_ln" in name \
-        or "embed_ln" in name
+        or "embed_ln" in name or (name.startswith("convnext.") and
+                                  ("_ln." in name or name.endswith(".gamma")))
 
 
 class ParamStore:
@@ -204,11 +205,28 @@ def init_normal(store: ParamStore, seed: int = 0, std: float = 0.02, cfg=None) -
     generated on the CPU so every rank / the oracle see identical bits."""
     g = torch.Generator().manual_seed(seed)
     for name, shape in store.shapes.items():
+        if name.startswith("convnext."):  # ConvNextPreTrainedModel._init_weights: N(0, std) conv
+            # and Linear weights, zero biases, unit LayerNorm gains, gamma = layer_scale_init
+            if name.endswith(".gamma"):
+                t = torch.full(shape, cfg.convnext.layer_scale_init if cfg is not None else 1e-6)
+            elif name.endswith(".bias"):
+                t = torch.zeros(shape)
+            elif name.endswith(("ln.weight", "ln_post.weight")):
+                t = torch.ones(shape)
+            else:
+                t = torch.randn(shape, generator=g) * std
+                if name == "convnext.stem.weight" and cfg is not None:  # im2col pad columns
+                    cn = cfg.convnext
+                    t[:, cn.channels * cn.patch * cn.patch:] = 0
+            store.load({name: t})
+            continue
         if name.endswith(("ln1.weight", "ln2.weight", "final_ln.weight", "ln_pre.weight",
                           "ln_post.weight", "embed_ln.weight", "mlm.ln.weight")):
             t = torch.ones(shape)
         else:
             t = torch.randn(shape, generator=g) * std
+        if cfg is not None and cfg.convnext is not None and name == "cls_head.bias":
+            t = torch.zeros(shape)  # HF: zero Linear biases
         if name == "vision.patch.weight" and cfg is not None:  # im2col pad columns stay 0
             v = cfg.vision
             t[:, v.channels * v.patch * v.patch:] = 0

@@ -53,6 +53,10 @@ def unit_of(name: str) -> str | None:
         return "text.lm_head"
     if name.startswith("cls_head."):
         return "cls_head"
+    if name.startswith("convnext.stem."):
+        return "convnext.stem"
+    if name.startswith("convnext.stages."):  # one unit per ConvNextStage (the reference's FSDP wrap)
+        return ".".join(name.split(".")[:3])
     if name.startswith("text.mlm."):  # RoBERTa's MLM head: dense and the decoder bias
         return "text.mlm"
     raise KeyError(f"no ZeRO-3 unit for parameter {name!r}")

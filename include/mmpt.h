@@ -699,6 +699,72 @@ int mmpt_unpatchify2_nhwc(int64_t B, int64_t H, int64_t W, int64_t C, const void
                           void* stream);
 
 /* ------------------------------------------------------------------------
+ * K22  Mamba (tf:models/mamba/modeling_mamba.py MambaMixer): the causal depthwise conv1d and the
+ * selective scan, the two ops the reference takes from causal-conv1d and mamba-ssm.  Rows are
+ * tokens (b, t), T = B*L rows in all; channels are contiguous and every activation has an explicit
+ * leading dimension, so x and z are read in place as the halves of the in_proj output [T][2I] and
+ * B and C as columns of the x_proj output [T][R+2N].  L is an argument: no kernel reads across a
+ * sequence boundary — a tap before t = 0 (or a gradient tap past t = L-1) is zero, never loaded.
+ * bf16 activations, fp32 arithmetic, one bf16 rounding where a result is stored.  Reductions over
+ * tokens or channels are per-workgroup partials summed in a fixed order by a second kernel: no
+ * atomics, bitwise reproducible.  Added without a change of MMPT_ABI_VERSION: the entries are new.
+ * B, L >= 1 with B*L < 2^31; bad arguments return MMPT_ERR_ARG and launch nothing.
+ * ---------------------------------------------------------------------- */
+/* Causal conv (K = 4, C % 8 == 0, C <= 65536; 16-B aligned pointers, leading dimensions multiples
+ * of 8 and >= C):  c = bf16(Σ_k w[k][ch] * x[b, t-(K-1)+k, ch] + bias[ch]) in fp32 over the taps
+ * with t-(K-1)+k >= 0, u = bf16(silu(f32(c))).  x bf16 [T][ld_x], w bf16 [K][C] (tap-major: HF's
+ * [C][1][K] transposed), bias bf16 [C], u bf16 [T][ld_u]. */
+int mmpt_causal_conv1d_fwd(int64_t B, int64_t L, int64_t C, int64_t K, const void* x, int64_t ld_x,
+                           const void* w, const void* bias, void* u, int64_t ld_u, void* stream);
+int64_t mmpt_causal_conv1d_bwd_workspace_bytes(int64_t B, int64_t L, int64_t C);
+/* dc = bf16((f32(du) + f32(du2)) * silu'(c)), c recomputed from x as in the forward (not stored);
+ * du2 (bf16 [T][ld_du2], NULL: zero) is a second gradient of u — u feeds the scan and x_proj, and
+ * x_proj's input gradient needs the dB / dC the scan's backward writes, so it joins here;
+ *   dx[b,t]  = bf16(Σ_k w[k] * dc[b, t+(K-1)-k])   over the taps with t+(K-1)-k < L
+ *   dw[k][ch] += f32(bf16(Σ_{b,t} dc[b,t,ch] * x[b, t-(K-1)+k, ch])),  db[ch] += f32(bf16(Σ dc))
+ * (the MMPT_EPI_F32_ACC convention).  du bf16 [T][ld_du], dx bf16 [T][ld_dx] (the first half of
+ * the d[x|z] buffer), dw fp32 [K][C], db fp32 [C]. */
+int mmpt_causal_conv1d_bwd(int64_t B, int64_t L, int64_t C, int64_t K, const void* x, int64_t ld_x,
+                           const void* w, const void* bias, const void* du, int64_t ld_du,
+                           const void* du2, int64_t ld_du2, void* dx, int64_t ld_dx, float* dw,
+                           float* db, void* workspace, void* stream);
+/* Selective scan (I % 8 == 0, N 8 or 16, B <= 65535; B, C, A_log, states and the workspace 16-B
+ * aligned, ld_bc a multiple of 8, the other leading dimensions >= I), fp32 from these operands:
+ *   δ = softplus(f32(dt_raw) + dt_bias)  (threshold 20),  a = -exp(A_log)
+ *   h_t = exp(δ_t a) h_{t-1} + δ_t B_t u_t,  h_{-1} = 0
+ *   y_t = bf16((Σ_n C_{t,n} h_{t,n} + D u_t) * silu(f32(z_t)))
+ * u, dt_raw, z, y bf16 [T][ld]; B, C bf16 [T][ld_bc] (N columns each); dt_bias, D fp32 [I]; A_log
+ * fp32 [I][N].  The sequence is cut into chunks of MMPT_SCAN_CHUNK tokens that run in parallel
+ * (a chunk's decay is exp(a Σδ)); the chunk length does not depend on L, so the first L' outputs
+ * of a longer sequence have the bits of a length-L' run when L' is a multiple of the chunk.
+ * `states` (nullable: then they stay in the workspace) receives the chunk-entry states, fp32
+ * [B][chunks][I][N], mmpt_selective_scan_states_bytes of them, for the backward. */
+#define MMPT_SCAN_CHUNK 32
+int64_t mmpt_selective_scan_chunk(void);
+int64_t mmpt_selective_scan_states_bytes(int64_t B, int64_t L, int64_t I, int64_t N);
+int64_t mmpt_selective_scan_fwd_workspace_bytes(int64_t B, int64_t L, int64_t I, int64_t N);
+int mmpt_selective_scan_fwd(int64_t B, int64_t L, int64_t I, int64_t N, const void* u,
+                            int64_t ld_u, const void* dt_raw, int64_t ld_dt, const float* dt_bias,
+                            const float* A_log, const void* Bm, const void* Cm, int64_t ld_bc,
+                            const float* D, const void* z, int64_t ld_z, void* y, int64_t ld_y,
+                            float* states, void* workspace, void* stream);
+int64_t mmpt_selective_scan_bwd_workspace_bytes(int64_t B, int64_t L, int64_t I, int64_t N);
+/* From dy bf16 [T][ld_dy] and the forward's operands and states (needed when L > MMPT_SCAN_CHUNK):
+ *   du  = bf16(f32(du_in) + scan gradient)  (du_in bf16, NULL: zero; may alias du)
+ *   dz, ddt_raw bf16 [T][ld];  dB, dC bf16 [T][ld_dbc] (sums over channels)
+ *   dA_log[I][N] += (Σ_t dα-terms) * a,  dD[I] +=,  ddt_bias[I] +=   fp32, summed over tokens from
+ *   the unrounded fp32 values.
+ * h_{t-1} in the backward is always recomputed forward from a chunk-entry state. */
+int mmpt_selective_scan_bwd(int64_t B, int64_t L, int64_t I, int64_t N, const void* u,
+                            int64_t ld_u, const void* dt_raw, int64_t ld_dt, const float* dt_bias,
+                            const float* A_log, const void* Bm, const void* Cm, int64_t ld_bc,
+                            const float* D, const void* z, int64_t ld_z, const float* states,
+                            const void* dy, int64_t ld_dy, const void* du_in, int64_t ld_du_in,
+                            void* du, int64_t ld_du, void* dz, int64_t ld_dz, void* ddt_raw,
+                            int64_t ld_ddt, void* dB, void* dC, int64_t ld_dbc, float* dA_log,
+                            float* dD, float* ddt_bias, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------
  * ZeRO++ quantized communication (sharding = "zero_3++"): replaces DeepSpeed's
  * `zero_quantized_weights` / `zero_quantized_gradients` kernels that
  * src/train.py:196-201 switches on.  Blockwise symmetric quantization, 256-element

@@ -128,6 +128,19 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_avgpool_bwd": (I32, [I64, I64, I64, P, P, P]),
     "mmpt_patchify2_nhwc": (I32, [I64, I64, I64, I64, P, P, P]),
     "mmpt_unpatchify2_nhwc": (I32, [I64, I64, I64, I64, P, P, P]),
+    "mmpt_causal_conv1d_fwd": (I32, [I64, I64, I64, I64, P, I64, P, P, P, I64, P]),
+    "mmpt_causal_conv1d_bwd_workspace_bytes": (I64, [I64, I64, I64]),
+    "mmpt_causal_conv1d_bwd": (I32, [I64, I64, I64, I64, P, I64, P, P, P, I64, P, I64, P, I64, P, P, P,
+                                     P]),
+    "mmpt_selective_scan_chunk": (I64, []),
+    "mmpt_selective_scan_states_bytes": (I64, [I64, I64, I64, I64]),
+    "mmpt_selective_scan_fwd_workspace_bytes": (I64, [I64, I64, I64, I64]),
+    "mmpt_selective_scan_fwd": (I32, [I64, I64, I64, I64, P, I64, P, I64, P, P, P, P, I64, P, P, I64,
+                                      P, I64, P, P, P]),
+    "mmpt_selective_scan_bwd_workspace_bytes": (I64, [I64, I64, I64, I64]),
+    "mmpt_selective_scan_bwd": (I32, [I64, I64, I64, I64, P, I64, P, I64, P, P, P, P, I64, P, P, I64,
+                                      P, P, I64, P, I64, P, I64, P, I64, P, I64, P, P, I64, P, P, P,
+                                      P, P]),
 }
 
 

@@ -24,7 +24,7 @@ import torch.distributed as dist
 
 from . import config as C
 from .distributed import sharding_to_mode
-from .optim import AdamConfig
+from .optim import AdamConfig, min_lr_rate_of
 from .trainer import ManualTrainer as _StepTrainer
 from .trainer import StepConfig
 
@@ -82,7 +82,7 @@ class ManualTrainer:
                               offload=tc.offload(),
                               scheduler=getattr(tc.scheduler_type, "value", tc.scheduler_type),
                               num_warmup_steps=warm, num_training_steps=tc.num_training_steps,
-                              min_lr_rate=sched_kw.get("min_lr_rate", 0.0))
+                              min_lr_rate=min_lr_rate_of(sched_kw, adam.lr))
         if sharding_to_mode(sharding) in ("zero2", "zero3") and model.mmpt_config.classifier:
             raise NotImplementedError(  # before partition_out releases the module's storage
                 f"sharding {sharding!r} for the vision-only classifier "
@@ -91,6 +91,11 @@ class ManualTrainer:
         if sharding_to_mode(sharding) in ("zero2", "zero3") and model.mmpt_config.text.roberta:
             raise NotImplementedError(  # before partition_out releases the module's storage
                 f"sharding {sharding!r} for the roberta masked LM "
+                f"{C.preset_name(model.mmpt_config)!r} is not implemented (data parallel and "
+                "zero_1 are)")
+        if sharding_to_mode(sharding) in ("zero2", "zero3") and model.mmpt_config.text.mamba:
+            raise NotImplementedError(  # before partition_out releases the module's storage
+                f"sharding {sharding!r} for the mamba language model "
                 f"{C.preset_name(model.mmpt_config)!r} is not implemented (data parallel and "
                 "zero_1 are)")
         if sharding_to_mode(sharding) in ("zero2", "zero3") and \

@@ -80,7 +80,13 @@ class TextConfig:
     post-LN encoder (LayerNorm after each residual add), learned positions counted from
     pad_id + 1 over the non-pad ids, a LayerNorm over the summed word / position / type
     embeddings, non-causal attention, erf-GELU MLP, the MLM head (dense, GELU, LayerNorm, the
-    decoder tied to the embedding plus a bias of its own), no label shift."""
+    decoder tied to the embedding plus a bias of its own), no label shift.
+    arch "mamba": Mamba (tf:models/mamba, the reference's src/models/mamba.py) — a stack of
+    MambaBlocks: RMSNorm of the fp32 residual, then the mixer (in_proj to x | z, a causal
+    depthwise conv of d_conv taps + SiLU over x, x_proj to dt | B | C, dt_proj, the selective scan
+    over d_state states per channel gated by silu(z), out_proj) added back to the residual; a final
+    RMSNorm and a decoder tied to the embedding.  No attention: `heads`, `ffn` and the rotary
+    fields are unused.  No dropout of either kind (MambaConfig has none)."""
 
     hidden: int = 2048
     layers: int = 16
@@ -110,10 +116,27 @@ class TextConfig:
     max_positions: int = 0
     pad_id: int = 1
     type_vocab: int = 1
+    # arch "mamba": MambaConfig.state_size / conv_kernel / expand / time_step_rank (0 = "auto",
+    # ceil(hidden / 16)); the conv has a bias, the linears have none
+    d_state: int = 16
+    d_conv: int = 4
+    expand: int = 2
+    dt_rank: int = 0
 
     def __post_init__(self):
         _check_dropout(self.hidden_dropout, "TextConfig")
         _check_dropout(self.attn_dropout, "TextConfig", "attn_dropout (attention_dropout)")
+        if self.arch == "mamba":
+            if self.hidden_dropout or self.attn_dropout:
+                raise ValueError("arch 'mamba': MambaConfig has no hidden or attention dropout")
+            if self.rotary_pct != 0 or not self.tie_embeddings or self.kv_heads or \
+                    self.rope_scaling is not None:
+                raise ValueError("arch 'mamba': rotary_pct 0, tied embeddings, no GQA, no rope scaling")
+            if self.d_conv != 4 or self.d_state not in (8, 16):
+                raise ValueError("arch 'mamba': d_conv 4 and d_state 8 or 16 (the scan kernels' sizes)")
+            if self.expand < 1 or self.dt_rank < 0 or self.d_inner % 8 or self.rank % 8:
+                raise ValueError("arch 'mamba': d_inner = expand * hidden and the dt rank must be "
+                                 f"multiples of 8 (16-B GEMM rows), got {self.d_inner} and {self.rank}")
         if self.hidden_dropout > 0 and self.arch == "llama":
             raise ValueError("hidden_dropout > 0 on a Llama text model: LlamaConfig has no "
                              "hidden dropout")
@@ -141,6 +164,24 @@ class TextConfig:
     @property
     def roberta(self) -> bool:
         return self.arch == "roberta"
+
+    @property
+    def mamba(self) -> bool:
+        return self.arch == "mamba"
+
+    @property
+    def d_inner(self) -> int:
+        return self.expand * self.hidden
+
+    @property
+    def rank(self) -> int:
+        """dt_rank, "auto" (0) resolved as MambaConfig does: ceil(hidden / 16)"""
+        return self.dt_rank or -(-self.hidden // 16)
+
+    @property
+    def xproj_dim(self) -> int:
+        """x_proj's rows: the low-rank dt input, then B and C"""
+        return self.rank + 2 * self.d_state
 
     def check_seq(self, seq: int) -> None:
         """RoBERTa's position ids reach seq + pad_id: a longer sequence has no table row."""
@@ -368,6 +409,20 @@ PRESETS["tiny-roberta"] = ModelConfig(text=_roberta(128, 2, 2, 256, 520, 515, 66
 PRESETS["tiny-roberta-drop"] = ModelConfig(text=_roberta(128, 2, 2, 256, 520, 515, 66, 0.1))
 
 
+def _mamba(h, L, V, V_valid=0, rank=0, state=16):
+    return TextConfig(hidden=h, layers=L, heads=1, ffn=0, vocab=V, vocab_valid=V_valid,
+                      rotary_pct=0.0, eps=1e-5, arch="mamba", tie_embeddings=True, d_state=state,
+                      d_conv=4, expand=2, dt_rank=rank)
+
+
+# the reference's `mamba` (src/models/mamba.py: MambaConfig.from_pretrained(
+# "state-spaces/mamba-2.8b-hf")), its published values written out: hidden 2560, 64 layers,
+# d_inner 5120, 16 states, 4 taps, dt rank 160, vocabulary 50280; everything else is MambaConfig's
+# default (RMSNorm eps 1e-5, conv bias, no linear biases, fp32 residual)
+PRESETS["mamba-2.8b"] = ModelConfig(text=_mamba(2560, 64, 50280, rank=160))
+PRESETS["tiny-mamba"] = ModelConfig(text=_mamba(128, 2, 520, 515, rank=8))
+
+
 def with_dropout(cfg: ModelConfig, text: float = 0.0, vision: float = 0.0, *,
                  text_attention: float = 0.0, vision_attention: float = 0.0) -> ModelConfig:
     """`cfg` with the dropout probabilities set.  Hidden dropout: `text` on a GPTNeoX language
@@ -484,6 +539,22 @@ def param_shapes(cfg: ModelConfig) -> dict[str, tuple[int, ...]]:
         s["proj.fc2.weight"] = (t.hidden, t.hidden)
         s["proj.fc2.bias"] = (t.hidden,)
     s["text.embed"] = (t.vocab, t.hidden)
+    if t.mamba:
+        I, R, N = t.d_inner, t.rank, t.d_state
+        for i in range(t.layers):
+            p = f"text.layers.{i}."
+            s[p + "norm.weight"] = (t.hidden,)            # MambaBlock.norm (RMS)
+            s[p + "in_proj.weight"] = (2 * I, t.hidden)   # x | z
+            s[p + "conv.weight"] = (t.d_conv, I)          # tap-major (HF: [I, 1, d_conv])
+            s[p + "conv.bias"] = (I,)
+            s[p + "x_proj.weight"] = (R + 2 * N, I)       # dt | B | C
+            s[p + "dt_proj.weight"] = (I, R)
+            s[p + "dt_proj.bias"] = (I,)
+            s[p + "A_log"] = (I, N)
+            s[p + "D"] = (I,)
+            s[p + "out_proj.weight"] = (t.hidden, I)
+        s["text.final_ln.weight"] = (t.hidden,)           # norm_f; the decoder is text.embed
+        return s
     if t.llama:
         for i in range(t.layers):
             p = f"text.layers.{i}."
@@ -594,6 +665,18 @@ def _roberta_flops(t: TextConfig, S: int) -> float:
     return 3.0 * (t.layers * layer + 2 * S * t.hidden * t.hidden + 2 * S * t.hidden * t.n_vocab)
 
 
+def _mamba_flops(t: TextConfig, S: int) -> float:
+    """3 × the matmul FLOPs of the five linears of every MambaBlock (in_proj, x_proj, dt_proj,
+    out_proj: 2S·(h·2I + I·(R+2N) + R·I + I·h)) plus the tied decoder over the real vocabulary.
+    The convention: FlopCounterMode counts matrix multiplications only, so the conv's and the
+    scan's elementwise work (in HF's torch path and in the fused kernels alike) is not counted,
+    here or in the executed count — there is no attention and every row is scored, so the two
+    counts are the same number."""
+    I, R, N = t.d_inner, t.rank, t.d_state
+    layer = 2 * S * (t.hidden * 2 * I + I * (R + 2 * N) + R * I + I * t.hidden)
+    return 3.0 * (t.layers * layer + 2 * S * t.hidden * t.n_vocab)
+
+
 def flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     """Algorithmic fwd+bwd FLOPs per sample in the reference's convention
     (src/benchmarking/flops.py:9-37: FlopCounterMode over one fwd+bwd, eager
@@ -607,6 +690,8 @@ def flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     t = cfg.text
     if t.roberta:
         return _roberta_flops(t, seq_text)
+    if t.mamba:
+        return _mamba_flops(t, seq_text)
     S = seq_text + (cfg.vision.num_patches if cfg.vision else 0)
     if t.llama:  # q,o: h^2 each; k,v: h*kv_dim each; gate, up, down: h*F each
         kvd = t.n_kv * t.head_dim
@@ -642,6 +727,8 @@ def executed_flops_per_sample(cfg: ModelConfig, seq_text: int) -> float:
     t = cfg.text
     if t.roberta:
         return _roberta_flops(t, seq_text)
+    if t.mamba:
+        return _mamba_flops(t, seq_text)
     n_img = cfg.vision.num_patches if cfg.vision else 0
     S = seq_text + n_img
     scored = seq_text - 1 if cfg.vision else S  # text-only batches keep every row (<5% unscored)

@@ -30,6 +30,11 @@ tf:models/convnext/modeling_convnext.py) keeps its activations channels-last: ro
 columns c.  The 7x7 depthwise conv, the layer-scale residual, the pool and the 2x2 patch
 permutations are include/mmpt.h K21; every 1x1 conv, the 4x4 stem and the 2x2 downsample are
 GEMMs over those rows (_convnext_forward / _convnext_backward).
+
+A Mamba language model (TextConfig.arch "mamba": MambaForCausalLM,
+tf:models/mamba/modeling_mamba.py) has no attention: each block is an RMSNorm, five GEMMs, the
+causal conv and the selective scan of include/mmpt.h K22, with the arithmetic of the reference's
+fused path (_mamba_forward / _mamba_backward).
 """
 
 from __future__ import annotations
@@ -171,6 +176,9 @@ class Batch:
         self.lens = [self.S] * self.B
         self.cu_seqlens = self.pos = None
         mask = self._check_mask(attention_mask)
+        if mask is not None and cfg.text.mamba:
+            raise ValueError("arch 'mamba': attention_mask has zeros — padded batches are not "
+                             "built for this model (the scan and the conv run over whole rows)")
         self._ready = None
         if stream is not None and device.type == "cuda":
             with torch.cuda.stream(stream):
@@ -436,7 +444,7 @@ class Engine:
         self.dev = store.device
         t = cfg.text
         self.cos = self.sin = None  # a vision-only classifier has no rope
-        if t is not None and not t.roberta:  # (RoBERTa: learned positions)
+        if t is not None and not t.roberta and not t.mamba:  # (RoBERTa: learned positions)
             if t.llama:
                 cos, sin = rope_tables_llama3(t.head_dim, t.rope_theta, t.rope_scaling, max_seq)
             else:
@@ -476,7 +484,8 @@ class Engine:
         store.transposed = [n for n in store.shapes if len(store.shapes[n]) == 2 and
                             n not in ("vision.patch.weight", "text.embed", "vision.pos",
                                       "text.pos_embed", "text.type_embed",
-                                      "convnext.stem.weight") and not n.endswith(".dw.weight")]
+                                      "convnext.stem.weight") and
+                            not n.endswith((".dw.weight", ".conv.weight", ".A_log"))]
         if tied:  # the tied lm_head's input gradient reads E^T
             store.transposed.append("text.embed")
         if self.frozen and not t.llama:
@@ -1564,6 +1573,143 @@ class Engine:
         self._join_side()
         self.cache.clear()
 
+    # -------------------------------------------------------------- mamba
+    _scan_keep = True  # the forward in flight hands the scan's chunk states to a backward
+
+    def _mamba_layer_fwd(self, i, x, B, S):
+        """MambaBlock (tf:models/mamba/modeling_mamba.py) with the fused arithmetic of the
+        reference's fast path: x' = x + bf16(out_proj(scan(silu(conv(xs)), ...) * silu(z))) with
+        xs | z = in_proj(RMS x), dt | B | C = x_proj(u), dt_raw = dt_proj.weight · dt (the bias is
+        added inside the scan, in fp32)."""
+        t = self.cfg.text
+        T, h, I, R, N = x.shape[0], t.hidden, t.d_inner, t.rank, t.d_state
+        p = f"text.layers.{i}."
+        y, r = self._e(T, h), self._e(T, dtype=F32)
+        K.rmsnorm_fwd(x, self.s.p(p + "norm.weight"), t.eps, y, r)
+        xz = self._linear(y, p + "in_proj", bias=False)
+        u = self._e(T, I)
+        K.causal_conv1d_fwd(xz[:, :I], self.s.w(p + "conv.weight"), self.s.w(p + "conv.bias"), u, S)
+        proj = self._linear(u, p + "x_proj", bias=False)
+        dt = self._e(T, I)
+        K.gemm(proj[:, :R], self.s.w(p + "dt_proj.weight"), dt)
+        ckpt = self.checkpointing and not self._recomputing
+        states = K.scan_states(B, S, I, N, self.dev) if self._scan_keep and not ckpt else None
+        ys = self._e(T, I)
+        K.selective_scan_fwd(u, dt, self.s.p(p + "dt_proj.bias"), self.s.p(p + "A_log"),
+                             proj[:, R:R + N], proj[:, R + N:], self.s.p(p + "D"), xz[:, I:], ys, S,
+                             states=states)
+        xn = self._linear(ys, p + "out_proj", bias=False, epi=K.EPI_F32_RESID, out2=x)
+        if ckpt:
+            self.cache[("t", i)] = ("ckpt", x)
+        else:
+            self.cache[("t", i)] = (x, r, y, xz, u, proj, dt, ys, states)
+        return xn
+
+    def _mamba_layer_bwd(self, i, dxn, ds, B, S):
+        """dxn: fp32 gradient of block i's output, ds = bf16(dxn) (out_proj's output gradient).
+        Returns (dx, bf16(dx)) for block i-1."""
+        t = self.cfg.text
+        T, h, I, R, N = dxn.shape[0], t.hidden, t.d_inner, t.rank, t.d_state
+        p = f"text.layers.{i}."
+        g = self.s.g
+        self._side_fence()
+        self._unit_bwd(f"text.layers.{i}")
+        self._restore(("t", i), self._mamba_layer_fwd, i, B, S)
+        x, r, y, xz, u, proj, dt, ys, states = self.cache.pop(("t", i))
+        dys = self._dx(ds, p + "out_proj")
+        self._dw(ds, ys, p + "out_proj", bias=False)
+        dxz, dproj = self._e(T, 2 * I), self._e(T, R + 2 * N)
+        du, ddt = self._e(T, I), self._e(T, I)
+        K.selective_scan_bwd(u, dt, self.s.p(p + "dt_proj.bias"), self.s.p(p + "A_log"),
+                             proj[:, R:R + N], proj[:, R + N:], self.s.p(p + "D"), xz[:, I:], dys,
+                             du, dxz[:, I:], ddt, dproj[:, R:R + N], dproj[:, R + N:],
+                             g(p + "A_log"), g(p + "D"), g(p + "dt_proj.bias"), S, states=states)
+        K.gemm(ddt, self.s.wt(p + "dt_proj.weight"), dproj[:, :R])
+        self._dw(ddt, proj[:, :R], p + "dt_proj", bias=False)
+        # u feeds the scan and x_proj: the conv's backward sums the two gradients in fp32
+        du2 = self._dx(dproj, p + "x_proj")
+        self._dw(dproj, u, p + "x_proj", bias=False)
+        K.causal_conv1d_bwd(xz[:, :I], self.s.w(p + "conv.weight"), self.s.w(p + "conv.bias"), du,
+                            dxz[:, :I], g(p + "conv.weight"), g(p + "conv.bias"), S, du2=du2)
+        dy = self._dx(dxz, p + "in_proj")
+        self._dw(dxz, y, p + "in_proj", bias=False)
+        nxt = self._e(T, h) if i > 0 else None
+        K.rmsnorm_bwd(x, r, dy, self.s.p(p + "norm.weight"), dxn, dw=self._gw(p + "norm"),
+                      dresid=dxn, dx_bf16=nxt)
+        self._unit_done(f"text.layers.{i}")
+        return dxn, nxt
+
+    def _mamba_forward(self, batch: Batch, grad_scale: float, need_grad: bool) -> torch.Tensor:
+        """MambaForCausalLM: the embedding gather, the blocks, the final RMSNorm, the decoder tied
+        to the embedding, Σ CE over the shifted labels.  need_grad = False keeps no scan states."""
+        t = self.cfg.text
+        if batch.cu_seqlens is not None:
+            raise ValueError("arch 'mamba': a batch with zeros in attention_mask — padding is not "
+                             "built for this model")
+        B, S, T = batch.B, batch.S, batch.T
+        if self.dev.type == "cuda":
+            batch.use(torch.cuda.current_stream(self.dev))
+        region = getattr(self.units, "region", None)
+        if region is not None:
+            region()
+        self._drop_begin(need_grad)
+        self._scan_keep = need_grad
+        h = self._e(T, t.hidden, dtype=F32)
+        self._f32_fwd("text.embed")
+        K.embed_fwd(batch.ids, self.s.p("text.embed"), h, None, None)
+        for i in range(t.layers):
+            self._unit_fwd(f"text.layers.{i}")
+            h = self._mamba_layer_fwd(i, h, B, S)
+        self._scan_keep = True  # a checkpoint recompute runs for a backward
+        yf, rf = self._e(T, t.hidden), self._e(T, dtype=F32)
+        K.rmsnorm_fwd(h, self.s.p("text.final_ln.weight"), t.eps, yf, rf)
+        if batch.loss_rows is not None:
+            yv = self._e(batch.loss_rows.numel(), t.hidden)
+            K.gather_rows(yf, batch.loss_rows, yv)
+            yf = yv
+        logits = self._e(yf.shape[0], t.vocab)
+        K.gemm(yf, self.s.w("text.embed"), logits)
+        loss_rows = self._e(yf.shape[0], dtype=F32)
+        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
+                        logits if need_grad else None, vocab_valid=t.n_vocab)
+        loss = self._e(1, dtype=F32)
+        K.sum_f32(loss_rows, loss)
+        if need_grad:
+            self.cache["head"] = (h, rf, yf, logits)
+        else:
+            self.cache.clear()
+        return loss
+
+    def _mamba_backward(self, batch: Batch, scale: torch.Tensor | None) -> None:
+        """Mirrors _mamba_forward; text.embed's gradient is the decoder's weight gradient plus the
+        gather's deterministic scatter-add."""
+        t = self.cfg.text
+        B, S, T = batch.B, batch.S, batch.T
+        hL, rf, yf, dlogits = self.cache.pop("head")
+        if scale is not None:
+            dlogits.mul_(scale.to(torch.float32))
+        dyf = self._dx(dlogits, "text.embed")
+        self._dw(dlogits, yf, "text.embed", bias=False)
+        del dlogits
+        if batch.loss_map is not None:
+            dyc, dyf = dyf, self._e(T, t.hidden)
+            K.expand_rows(dyc, batch.loss_map, dyf)
+        dh, ds = torch.empty_like(hL), self._e(T, t.hidden)
+        K.rmsnorm_bwd(hL, rf, dyf, self.s.p("text.final_ln.weight"), dh,
+                      dw=self._gw("text.final_ln"), dx_bf16=ds)
+        self._ready(("text.final_ln.",))
+        for i in reversed(range(t.layers)):
+            dh, ds = self._mamba_layer_bwd(i, dh, ds, B, S)
+            self._ready((f"text.layers.{i}.",))
+        if self._side is not None:  # the decoder's weight gradient also lands in text.embed
+            torch.cuda.current_stream(self.dev).wait_stream(self._side)
+        self._f32_bwd("text.embed")
+        K.embed_bwd(batch.segments, dh, self.s.g("text.embed"), None, None)
+        self._f32_done("text.embed")
+        self._ready(("text.embed",))
+        self._join_side()
+        self.cache.clear()
+
     # -------------------------------------------------------------- whole model
     def forward(self, batch: Batch, grad_scale: float, need_grad: bool = True) -> torch.Tensor:
         """Returns Σ_tokens CE (device fp32 [1]); when need_grad, dlogits are written
@@ -1574,6 +1720,8 @@ class Engine:
             return self._cls_forward(batch, grad_scale, need_grad)
         if self.cfg.text.roberta:
             return self._roberta_forward(batch, grad_scale, need_grad)
+        if self.cfg.text.mamba:
+            return self._mamba_forward(batch, grad_scale, need_grad)
         cfg, t = self.cfg, self.cfg.text
         # S: the longest sequence — the padded width on the dense path, where T = B * S
         B, S, T = batch.B, batch.max_len, batch.T
@@ -1631,6 +1779,8 @@ class Engine:
             return self._cls_backward(batch, scale)
         if self.cfg.text.roberta:
             return self._roberta_backward(batch, scale)
+        if self.cfg.text.mamba:
+            return self._mamba_backward(batch, scale)
         cfg, t = self.cfg, self.cfg.text
         B, S, T = batch.B, batch.max_len, batch.T
         self._vl = batch if batch.cu_seqlens is not None else None

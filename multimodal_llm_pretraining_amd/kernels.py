@@ -989,3 +989,127 @@ def unpatchify2_nhwc(rows, dx) -> None:
         raise ValueError("unpatchify2_nhwc: H and W must be even")
     _dense(rows, torch.bfloat16, (B * (H // 2) * (W // 2), 4 * C), "unpatchify2_nhwc.rows")
     _lib.call("mmpt_unpatchify2_nhwc", B, H, W, C, rows.data_ptr(), dx.data_ptr(), _stream())
+
+
+# ----------------------------------------------------------------------------- Mamba (K22)
+# Rows are tokens (b, t): 2-D tensors [B*L, C] with unit inner stride and any row stride, so the
+# halves of the in_proj output and the columns of the x_proj output are passed as views.
+def scan_chunk() -> int:
+    """Tokens per chunk of the selective scan (fixed: it does not depend on L)."""
+    return int(_lib.query("mmpt_selective_scan_chunk"))
+
+
+def _tokens(t, rows, cols, name) -> int:
+    ld = _rows_bf16(t, rows, cols, name)
+    if rows == 1:  # a single row has no stride to speak of; torch reports anything
+        ld = max(ld, cols)
+    return ld
+
+
+def _seq(rows: int, L: int, name: str) -> int:
+    if L <= 0 or rows % L:
+        raise ValueError(f"{name}: {rows} rows are not a whole number of length-{L} sequences")
+    return rows // L
+
+
+def causal_conv1d_fwd(x, w, bias, u, L: int) -> None:
+    """u = bf16(silu(bf16(causal_conv1d(x; w, bias)))): x, u bf16 [B*L, C], w bf16 [4, C]
+    tap-major, bias bf16 [C]; sequences of L rows, no tap crosses a sequence start."""
+    rows, C = x.shape
+    B = _seq(rows, L, "causal_conv1d_fwd")
+    ld_x = _tokens(x, rows, C, "causal_conv1d_fwd.x")
+    ld_u = _tokens(u, rows, C, "causal_conv1d_fwd.u")
+    _dense(w, torch.bfloat16, (4, C), "causal_conv1d_fwd.w")
+    _dense(bias, torch.bfloat16, (C,), "causal_conv1d_fwd.bias")
+    _lib.call("mmpt_causal_conv1d_fwd", B, L, C, 4, x.data_ptr(), ld_x, w.data_ptr(),
+              bias.data_ptr(), u.data_ptr(), ld_u, _stream())
+
+
+def causal_conv1d_bwd(x, w, bias, du, dx, dw, db, L: int, du2=None) -> None:
+    """dx = bf16(conv^T(dc)), dw [4, C] += bf16(Σ dc * x shifted), db [C] += bf16(Σ dc) with
+    dc = bf16((du + du2) * silu'(c)), c recomputed from x; dw, db fp32.  du2: a second gradient
+    of u (x_proj's input gradient beside the scan's), summed in fp32."""
+    rows, C = x.shape
+    B = _seq(rows, L, "causal_conv1d_bwd")
+    ld_x = _tokens(x, rows, C, "causal_conv1d_bwd.x")
+    ld_du = _tokens(du, rows, C, "causal_conv1d_bwd.du")
+    ld_dx = _tokens(dx, rows, C, "causal_conv1d_bwd.dx")
+    ld_du2 = 0 if du2 is None else _tokens(du2, rows, C, "causal_conv1d_bwd.du2")
+    _dense(w, torch.bfloat16, (4, C), "causal_conv1d_bwd.w")
+    _dense(bias, torch.bfloat16, (C,), "causal_conv1d_bwd.bias")
+    _dense(dw, torch.float32, (4, C), "causal_conv1d_bwd.dw")
+    _dense(db, torch.float32, (C,), "causal_conv1d_bwd.db")
+    ws = workspace(_lib.query("mmpt_causal_conv1d_bwd_workspace_bytes", B, L, C), slot=2)
+    _lib.call("mmpt_causal_conv1d_bwd", B, L, C, 4, x.data_ptr(), ld_x, w.data_ptr(),
+              bias.data_ptr(), du.data_ptr(), ld_du, _p(du2), ld_du2, dx.data_ptr(), ld_dx,
+              dw.data_ptr(), db.data_ptr(), ws.data_ptr(), _stream())
+
+
+def scan_states(B: int, L: int, I: int, N: int, device) -> torch.Tensor:
+    """An empty tensor for the chunk-entry states the scan's forward hands to its backward."""
+    chunks = (L + scan_chunk() - 1) // scan_chunk()
+    return torch.empty(B, chunks, I, N, dtype=torch.float32, device=device)
+
+
+def _scan_operands(name, u, dt_raw, dt_bias, A_log, Bm, Cm, D, z, L):
+    rows, I = u.shape
+    N = A_log.shape[1] if A_log.dim() == 2 else -1
+    B = _seq(rows, L, name)
+    ld = [_tokens(u, rows, I, name + ".u"), _tokens(dt_raw, rows, I, name + ".dt_raw"),
+          _tokens(Bm, rows, N, name + ".B"), _tokens(Cm, rows, N, name + ".C"),
+          _tokens(z, rows, I, name + ".z")]
+    if ld[2] != ld[3]:
+        raise ValueError(f"{name}: B and C must share a row stride ({ld[2]} vs {ld[3]})")
+    _dense(dt_bias, torch.float32, (I,), name + ".dt_bias")
+    _dense(A_log, torch.float32, (I, N), name + ".A_log")
+    _dense(D, torch.float32, (I,), name + ".D")
+    return B, rows, I, N, ld
+
+
+def selective_scan_fwd(u, dt_raw, dt_bias, A_log, Bm, Cm, D, z, y, L: int, states=None) -> None:
+    """y = bf16((Σ_n C h + D u) * silu(z)) with h_t = exp(δ a) h_{t-1} + δ B u,
+    δ = softplus(dt_raw + dt_bias), a = -exp(A_log).  u, dt_raw, z, y bf16 [B*L, I]; Bm, Cm bf16
+    [B*L, N]; `states` (from scan_states) receives the chunk-entry states for the backward."""
+    B, rows, I, N, ld = _scan_operands("selective_scan_fwd", u, dt_raw, dt_bias, A_log, Bm, Cm, D,
+                                       z, L)
+    ld_y = _tokens(y, rows, I, "selective_scan_fwd.y")
+    if states is not None:
+        _dense(states, torch.float32, (B, (L + scan_chunk() - 1) // scan_chunk(), I, N),
+               "selective_scan_fwd.states")
+    ws = workspace(_lib.query("mmpt_selective_scan_fwd_workspace_bytes", B, L, I, N), slot=2)
+    _lib.call("mmpt_selective_scan_fwd", B, L, I, N, u.data_ptr(), ld[0], dt_raw.data_ptr(), ld[1],
+              dt_bias.data_ptr(), A_log.data_ptr(), Bm.data_ptr(), Cm.data_ptr(), ld[2],
+              D.data_ptr(), z.data_ptr(), ld[4], y.data_ptr(), ld_y, _p(states), ws.data_ptr(),
+              _stream())
+
+
+def selective_scan_bwd(u, dt_raw, dt_bias, A_log, Bm, Cm, D, z, dy, du, dz, ddt_raw, dB, dC,
+                       dA_log, dD, ddt_bias, L: int, states=None, du_in=None) -> None:
+    """The scan's backward: du (= du_in + the scan's gradient), dz, ddt_raw, dB, dC bf16;
+    dA_log, dD, ddt_bias fp32, +=.  `states` is what the forward wrote (needed when L exceeds one
+    chunk)."""
+    name = "selective_scan_bwd"
+    B, rows, I, N, ld = _scan_operands(name, u, dt_raw, dt_bias, A_log, Bm, Cm, D, z, L)
+    ld_dy = _tokens(dy, rows, I, name + ".dy")
+    ld_du = _tokens(du, rows, I, name + ".du")
+    ld_dz = _tokens(dz, rows, I, name + ".dz")
+    ld_ddt = _tokens(ddt_raw, rows, I, name + ".ddt_raw")
+    ld_db = _tokens(dB, rows, N, name + ".dB")
+    if _tokens(dC, rows, N, name + ".dC") != ld_db:
+        raise ValueError(f"{name}: dB and dC must share a row stride")
+    ld_dui = 0 if du_in is None else _tokens(du_in, rows, I, name + ".du_in")
+    _dense(dA_log, torch.float32, (I, N), name + ".dA_log")
+    _dense(dD, torch.float32, (I,), name + ".dD")
+    _dense(ddt_bias, torch.float32, (I,), name + ".ddt_bias")
+    chunks = (L + scan_chunk() - 1) // scan_chunk()
+    if states is not None:
+        _dense(states, torch.float32, (B, chunks, I, N), name + ".states")
+    elif chunks > 1:
+        raise ValueError(f"{name}: L = {L} spans {chunks} chunks: the forward's states are needed")
+    ws = workspace(_lib.query("mmpt_selective_scan_bwd_workspace_bytes", B, L, I, N), slot=2)
+    _lib.call("mmpt_selective_scan_bwd", B, L, I, N, u.data_ptr(), ld[0], dt_raw.data_ptr(), ld[1],
+              dt_bias.data_ptr(), A_log.data_ptr(), Bm.data_ptr(), Cm.data_ptr(), ld[2],
+              D.data_ptr(), z.data_ptr(), ld[4], _p(states), dy.data_ptr(), ld_dy, _p(du_in),
+              ld_dui, du.data_ptr(), ld_du, dz.data_ptr(), ld_dz, ddt_raw.data_ptr(), ld_ddt,
+              dB.data_ptr(), dC.data_ptr(), ld_db, dA_log.data_ptr(), dD.data_ptr(),
+              ddt_bias.data_ptr(), ws.data_ptr(), _stream())

@@ -16,8 +16,11 @@ the LLaVA-pretrain recipe (src/models/llava.py:80-124) used for the C3 compositi
 freeze); `vit` / `vit-bf16` its ViT-L/16 image classifier (src/models/vit.py); model types
 `roberta` / `roberta-bf16` its RoBERTa-large masked LM (src/models/roberta.py);
 `convnext-large-1k` / `convnext-large-22k` / `convnext-xlarge-22k` (and their `-bf16` forms) its
-ConvNeXt image classifiers (src/models/convnext.py); model types outside the path (mamba,
-llava-finetune, vilt-*) raise.
+ConvNeXt image classifiers (src/models/convnext.py); `mamba-2.8b` its Mamba language model
+(src/models/mamba.py).  The reference's own name for that one, `mamba`, stays refused: its class
+fetches the configuration from the hub by that name, which this path never does — `mamba-2.8b`
+is the same model with the published hyper-parameters written out, as config.py writes out the
+Pythia and Llama configs.  Model types outside the path (mamba, llava-finetune, vilt-*) raise.
 """
 
 from __future__ import annotations
@@ -44,7 +47,8 @@ RobertaT = Literal["roberta", "roberta-bf16"]
 ConvNextT = Literal["convnext-large-1k", "convnext-large-22k", "convnext-xlarge-22k",
                     "convnext-large-1k-bf16", "convnext-large-22k-bf16",
                     "convnext-xlarge-22k-bf16"]
-ModelT = Literal[PythiaT, VitPythiaT, LlavaT, ViTT, RobertaT, ConvNextT]
+MambaT = Literal["mamba-2.8b"]
+ModelT = Literal[PythiaT, VitPythiaT, LlavaT, ViTT, RobertaT, ConvNextT, MambaT]
 # reference model types that are not on this path (out of scope;
 # llava-finetune needs a private checkpoint, src/models/llava.py:151)
 OUT_OF_SCOPE = ("mamba", "llava-finetune",
@@ -342,6 +346,40 @@ class ConvNextModelClass(BaseModelClass):
         return DummyImageClassificationDataset(self.image_size, self.num_classes, num_samples)
 
 
+class MambaModelClass(BaseModelClass):
+    """The reference's `mamba` (src/models/mamba.py:15-85) under the name `mamba-2.8b`:
+    MambaForCausalLM on the state-spaces/mamba-2.8b-hf configuration, written out in
+    config.PRESETS; batch 128, 572,204 steps, bf16, AdamW lr 8e-4 β (0.9, 0.95) wd 0.1,
+    cosine_with_min_lr with 10% warm-up down to an absolute min_lr of 1e-5, clip 1.0, sequences
+    of 4096 over a dataset vocabulary of 50265, no compilation."""
+
+    def build_model(self, use_custom_kernels: bool = True) -> nn.Module:
+        if use_custom_kernels:
+            return MMPTForPretraining(self.model_config)
+        return build_hf_model(self.model_config)
+
+    supports_compilation = property(lambda self: False)
+    batch_size = property(lambda self: 128)
+    training_steps = property(lambda self: 572_204)
+    mixed_precision = property(lambda self: "bf16")
+    optimizer = property(lambda self: torch.optim.AdamW)
+    optimizer_kwargs = property(lambda self: {"lr": (1.6e-4) * 5, "weight_decay": 0.1,
+                                              "betas": (0.9, 0.95)})
+    scheduler_type = property(lambda self: "cosine_with_min_lr")
+
+    @property
+    def scheduler_kwargs(self):
+        return {"num_warmup_steps": int(0.1 * self.training_steps), "min_lr": 1e-5}
+
+    max_grad_norm = property(lambda self: 1.0)
+    fsdp_layers_to_wrap = property(lambda self: ["MambaBlock"])
+    vocab_size = property(lambda self: 50265)
+    sequence_length = property(lambda self: 4096)
+
+    def load_dummy_dataset(self, num_samples: int = 50_000):
+        return DummyTextModelingDataset(self.vocab_size, self.sequence_length, num_samples)
+
+
 def get_model_class(model_type: str) -> BaseModelClass:
     """src/models/__init__.py:240-296 for the types on the MI355X path."""
     if model_type in PythiaModelClass._LR:
@@ -358,6 +396,8 @@ def get_model_class(model_type: str) -> BaseModelClass:
         return RobertaModelClass(model_type)
     if model_type in ConvNextT.__args__:
         return ConvNextModelClass(model_type)
+    if model_type in MambaT.__args__:
+        return MambaModelClass(model_type)
     if model_type in OUT_OF_SCOPE:
         raise NotImplementedError(f"model type {model_type!r} is not on the MI355X hot path "
                                   "(SURVEY.md §8 scope)")
@@ -462,6 +502,12 @@ class MMPTForPretraining(nn.Module):
             self.config = SimpleNamespace(hidden_size=t.hidden, text_config=text_cfg,
                                           use_cache=False, model_type="mmpt",
                                           image_token_index=cfg.image_token_id)
+            if t.mamba:  # MambaConfig's names, on the top-level config
+                self.config.vocab_size = t.n_vocab
+                self.config.num_hidden_layers = t.layers
+                self.config.state_size = t.d_state
+                self.config.intermediate_size = t.d_inner
+                self.config.time_step_rank = t.rank
             if t.roberta:  # a text-only model: HF keeps these on the top-level config
                 self.config.vocab_size = t.n_vocab
                 self.config.max_position_embeddings = t.max_positions
@@ -589,6 +635,17 @@ def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
             max_position_embeddings=t.max_positions, type_vocab_size=t.type_vocab,
             layer_norm_eps=t.eps, pad_token_id=t.pad_id, bos_token_id=0, eos_token_id=2,
             attn_implementation="eager"))
+    if t.mamba:
+        from transformers import MambaConfig, MambaForCausalLM
+
+        # state-spaces/mamba-2.8b-hf's public hyper-parameters written out (no hub access); the
+        # rest is MambaConfig's default.  Without mamba-ssm / causal-conv1d the module takes its
+        # torch path.  The vocabulary is the real one: padding rows exist only in the HIP layout
+        return MambaForCausalLM(MambaConfig(
+            vocab_size=t.n_vocab, hidden_size=t.hidden, state_size=t.d_state,
+            num_hidden_layers=t.layers, layer_norm_epsilon=t.eps, expand=t.expand,
+            conv_kernel=t.d_conv, time_step_rank=t.rank, use_bias=False, use_conv_bias=True,
+            residual_in_fp32=True, tie_word_embeddings=True))
     from transformers import GPTNeoXConfig, GPTNeoXForCausalLM
 
     tc = GPTNeoXConfig(vocab_size=t.vocab, hidden_size=t.hidden, num_hidden_layers=t.layers,

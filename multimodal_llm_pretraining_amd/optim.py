@@ -223,6 +223,17 @@ def lr_lambda(kind: str, step: int, num_warmup: int, num_training: int,
     raise ValueError(f"unsupported scheduler {kind!r}")
 
 
+def min_lr_rate_of(scheduler_kwargs: dict, base_lr: float) -> float:
+    """cosine_with_min_lr's floor as a rate of the base lr: `min_lr_rate`, or an absolute `min_lr`
+    over the base lr (transformers' get_cosine_with_min_lr_schedule_with_warmup takes either and
+    divides the same way); 0 when neither is given."""
+    if scheduler_kwargs.get("min_lr_rate") is not None:
+        return float(scheduler_kwargs["min_lr_rate"])
+    if scheduler_kwargs.get("min_lr") is not None:
+        return float(scheduler_kwargs["min_lr"]) / float(base_lr)
+    return 0.0
+
+
 class Schedule:
     def __init__(self, base_lr: float, kind: str, num_warmup_steps: int, num_training_steps: int,
                  min_lr_rate: float = 0.0):

@@ -26,7 +26,8 @@ def is_fp32_read(name: str) -> bool:
     return name in ("text.embed", "vision.pos", "vision.cls", "text.pos_embed",
                     "text.type_embed") or ".ln" in name or "final_ln" in name \
         or "embed_ln" in name or (name.startswith("convnext.") and
-                                  ("_ln." in name or name.endswith(".gamma")))
+                                  ("_ln." in name or name.endswith(".gamma"))) \
+        or name.endswith((".norm.weight", ".A_log", ".D", ".dt_proj.bias"))  # Mamba: HF's .float()
 
 
 class ParamStore:
@@ -196,6 +197,39 @@ class ParamStore:
             self.grad.zero_()
 
 
+def _mamba_init(name, shape, t, g) -> torch.Tensor:
+    """MambaPreTrainedModel._init_weights / MambaMixer.init_mamba_weights with MambaConfig's
+    defaults: Linear and embedding weights N(0, initializer_range = 0.1), A_log = log(1..N), D = 1,
+    dt_proj.weight U(±rank^-1/2), dt_proj.bias = softplus^-1(dt) with dt log-uniform in
+    [1e-3, 1e-1] floored at 1e-4, the conv and out_proj kaiming-uniform (a = √5: U(±fan_in^-1/2)),
+    the conv bias zero, RMSNorm gains one."""
+    import math
+
+    def uniform(bound):
+        return (torch.rand(shape, generator=g) * 2 - 1) * bound
+
+    if name.endswith(("norm.weight", "final_ln.weight", ".D")):
+        return torch.ones(shape)
+    if name.endswith(".A_log"):
+        return torch.log(torch.arange(1, shape[1] + 1, dtype=torch.float32)).expand(shape).clone()
+    if name.endswith(".conv.weight"):
+        return uniform(t.d_conv ** -0.5)
+    if name.endswith(".conv.bias"):
+        return torch.zeros(shape)
+    if name.endswith(".out_proj.weight"):
+        return uniform(t.d_inner ** -0.5)
+    if name.endswith(".dt_proj.weight"):
+        return uniform(t.rank ** -0.5)
+    if name.endswith(".dt_proj.bias"):
+        dt = torch.exp(torch.rand(shape, generator=g) * (math.log(0.1) - math.log(0.001))
+                       + math.log(0.001)).clamp(min=1e-4)
+        return dt + torch.log(-torch.expm1(-dt))
+    w = torch.randn(shape, generator=g) * 0.1
+    if name == "text.embed":
+        w[t.n_vocab:] = 0  # vocabulary padding rows (never read, zero gradient)
+    return w
+
+
 def _round(n: int, m: int) -> int:
     return (n + m - 1) // m * m
 
@@ -205,6 +239,9 @@ def init_normal(store: ParamStore, seed: int = 0, std: float = 0.02, cfg=None) -
     generated on the CPU so every rank / the oracle see identical bits."""
     g = torch.Generator().manual_seed(seed)
     for name, shape in store.shapes.items():
+        if cfg is not None and cfg.text is not None and cfg.text.mamba:
+            store.load({name: _mamba_init(name, shape, cfg.text, g)})
+            continue
         if name.startswith("convnext."):  # ConvNextPreTrainedModel._init_weights: N(0, std) conv
             # and Linear weights, zero biases, unit LayerNorm gains, gamma = layer_scale_init
             if name.endswith(".gamma"):

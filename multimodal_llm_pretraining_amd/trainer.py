@@ -76,6 +76,12 @@ class ManualTrainer:
                 f"sharding {step_cfg.sharding!r} for the roberta masked LM "
                 f"{C.preset_name(self.cfg) or step_cfg.model!r} is not implemented (data "
                 "parallel and zero_1 are)")
+        if mode in ("zero2", "zero3") and self.cfg.text.mamba:
+            # the per-unit partition has no gather for the fp32-read scan parameters of a block
+            raise NotImplementedError(
+                f"sharding {step_cfg.sharding!r} for the mamba language model "
+                f"{C.preset_name(self.cfg) or step_cfg.model!r} is not implemented (data "
+                "parallel and zero_1 are)")
         if mode == "zero3" and self.cfg.text.tie_embeddings:
             raise NotImplementedError("ZeRO-3 with a tied lm_head (Llama) is not implemented")
         # ZeRO-2 and ZeRO-3 share the per-unit partition (zero3.py): ZeRO-2 keeps the bf16

@@ -705,6 +705,8 @@ int mmpt_unpatchify2_nhwc(int64_t B, int64_t H, int64_t W, int64_t C, const void
  * leading dimension, so x and z are read in place as the halves of the in_proj output [T][2I] and
  * B and C as columns of the x_proj output [T][R+2N].  L is an argument: no kernel reads across a
  * sequence boundary — a tap before t = 0 (or a gradient tap past t = L-1) is zero, never loaded.
+ * The varlen entries at the end of this block take T packed rows of sequences of any lengths
+ * instead (positions and chunk offsets from int32 device tables) with the same arithmetic.
  * bf16 activations, fp32 arithmetic, one bf16 rounding where a result is stored.  Reductions over
  * tokens or channels are per-workgroup partials summed in a fixed order by a second kernel: no
  * atomics, bitwise reproducible.  Added without a change of MMPT_ABI_VERSION: the entries are new.
@@ -763,6 +765,55 @@ int mmpt_selective_scan_bwd(int64_t B, int64_t L, int64_t I, int64_t N, const vo
                             void* du, int64_t ld_du, void* dz, int64_t ld_dz, void* ddt_raw,
                             int64_t ld_ddt, void* dB, void* dC, int64_t ld_dbc, float* dA_log,
                             float* dD, float* ddt_bias, void* workspace, void* stream);
+/* K22 varlen: packed rows.  The T rows are n_seq sequences laid end to end (a Batch built from
+ * position_ids or a padding mask), every sequence at least one token long; the arithmetic per
+ * token and per chunk is that of the entries above (the same device code), so the per-token
+ * results of a sequence — u, dx, y, the states, du, dz, ddt_raw, dB, dC — have the bits of a dense
+ * call on that sequence alone (B = 1, L = its length).  The sums over tokens (dw, db, dA_log, dD,
+ * ddt_bias) are the same partials summed in another fixed order.  Integer tables are int32 in
+ * device memory, 4-byte aligned, passed as const void*; added without a change of
+ * MMPT_ABI_VERSION: the entries are new.
+ * Causal conv: pos [T], the position of each token inside its sequence.  Forward tap t-j exists
+ * iff pos[t] >= j; for dx, tap t+j exists iff t+j < T and pos[t+j] >= j.  A row outside the
+ * sequence is never loaded.  Other arguments as mmpt_causal_conv1d_fwd / _bwd. */
+int mmpt_causal_conv1d_varlen_fwd(int64_t T, int64_t C, int64_t K, const void* pos, const void* x,
+                                  int64_t ld_x, const void* w, const void* bias, void* u,
+                                  int64_t ld_u, void* stream);
+int64_t mmpt_causal_conv1d_varlen_bwd_workspace_bytes(int64_t T, int64_t C);
+int mmpt_causal_conv1d_varlen_bwd(int64_t T, int64_t C, int64_t K, const void* pos, const void* x,
+                                  int64_t ld_x, const void* w, const void* bias, const void* du,
+                                  int64_t ld_du, const void* du2, int64_t ld_du2, void* dx,
+                                  int64_t ld_dx, float* dw, float* db, void* workspace,
+                                  void* stream);
+/* Selective scan: chunks of MMPT_SCAN_CHUNK tokens are counted from each sequence's own start, so
+ * no chunk straddles a boundary and every carry, forward and reverse, starts from zero at a
+ * sequence's start and stops at its end.  cu_seqlens [n_seq + 1]: row offsets (cu[0] = 0,
+ * cu[n_seq] = T); cu_chunks [n_seq + 1]: chunk offsets, cu_chunks[s+1] - cu_chunks[s] =
+ * ceil(len_s / chunk); total_chunks = cu_chunks[n_seq] <= T / chunk + n_seq, given by the caller
+ * (the host never reads the tables).  n_seq <= 65535.  states fp32 [total_chunks][I][N]; needed by
+ * the backward when total_chunks > n_seq.  Other arguments as mmpt_selective_scan_fwd / _bwd. */
+int64_t mmpt_selective_scan_varlen_states_bytes(int64_t total_chunks, int64_t I, int64_t N);
+int64_t mmpt_selective_scan_varlen_fwd_workspace_bytes(int64_t total_chunks, int64_t I, int64_t N);
+int mmpt_selective_scan_varlen_fwd(int64_t T, int64_t n_seq, int64_t total_chunks,
+                                   const void* cu_seqlens, const void* cu_chunks, int64_t I,
+                                   int64_t N, const void* u, int64_t ld_u, const void* dt_raw,
+                                   int64_t ld_dt, const float* dt_bias, const float* A_log,
+                                   const void* Bm, const void* Cm, int64_t ld_bc, const float* D,
+                                   const void* z, int64_t ld_z, void* y, int64_t ld_y,
+                                   float* states, void* workspace, void* stream);
+int64_t mmpt_selective_scan_varlen_bwd_workspace_bytes(int64_t T, int64_t total_chunks, int64_t I,
+                                                       int64_t N);
+int mmpt_selective_scan_varlen_bwd(int64_t T, int64_t n_seq, int64_t total_chunks,
+                                   const void* cu_seqlens, const void* cu_chunks, int64_t I,
+                                   int64_t N, const void* u, int64_t ld_u, const void* dt_raw,
+                                   int64_t ld_dt, const float* dt_bias, const float* A_log,
+                                   const void* Bm, const void* Cm, int64_t ld_bc, const float* D,
+                                   const void* z, int64_t ld_z, const float* states,
+                                   const void* dy, int64_t ld_dy, const void* du_in,
+                                   int64_t ld_du_in, void* du, int64_t ld_du, void* dz,
+                                   int64_t ld_dz, void* ddt_raw, int64_t ld_ddt, void* dB,
+                                   void* dC, int64_t ld_dbc, float* dA_log, float* dD,
+                                   float* ddt_bias, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------
  * ZeRO++ quantized communication (sharding = "zero_3++"): replaces DeepSpeed's

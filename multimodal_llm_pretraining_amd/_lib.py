@@ -141,6 +141,19 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_selective_scan_bwd": (I32, [I64, I64, I64, I64, P, I64, P, I64, P, P, P, P, I64, P, P, I64,
                                       P, P, I64, P, I64, P, I64, P, I64, P, I64, P, P, I64, P, P, P,
                                       P, P]),
+    # K22 varlen: packed rows, positions / chunk offsets from int32 device tables
+    "mmpt_causal_conv1d_varlen_fwd": (I32, [I64, I64, I64, P, P, I64, P, P, P, I64, P]),
+    "mmpt_causal_conv1d_varlen_bwd_workspace_bytes": (I64, [I64, I64]),
+    "mmpt_causal_conv1d_varlen_bwd": (I32, [I64, I64, I64, P, P, I64, P, P, P, I64, P, I64, P, I64,
+                                            P, P, P, P]),
+    "mmpt_selective_scan_varlen_states_bytes": (I64, [I64, I64, I64]),
+    "mmpt_selective_scan_varlen_fwd_workspace_bytes": (I64, [I64, I64, I64]),
+    "mmpt_selective_scan_varlen_fwd": (I32, [I64, I64, I64, P, P, I64, I64, P, I64, P, I64, P, P, P,
+                                             P, I64, P, P, I64, P, I64, P, P, P]),
+    "mmpt_selective_scan_varlen_bwd_workspace_bytes": (I64, [I64, I64, I64, I64]),
+    "mmpt_selective_scan_varlen_bwd": (I32, [I64, I64, I64, P, P, I64, I64, P, I64, P, I64, P, P, P,
+                                             P, I64, P, P, I64, P, P, I64, P, I64, P, I64, P, I64,
+                                             P, I64, P, P, I64, P, P, P, P, P]),
 }
 
 

@@ -20,6 +20,12 @@
 //   backward  the same three steps in reverse for the adjoint of h, then the main pass: for each
 //             n it recomputes h_t of the chunk into registers and walks back.  h_{t-1} is always a
 //             recomputed value, never h_t divided by the decay.
+// Varlen forms (packed rows, T tokens of n_seq sequences laid end to end): the same kernels,
+// instantiated with VAR = true.  The conv reads each token's position inside its sequence (pos,
+// int32 [T]) and takes a tap only inside the sequence; the scan counts its chunks from each
+// sequence's own start, a workgroup finding its sequence by a binary search over the chunk offsets
+// (cu_chunks, int32 [n_seq + 1]), and the carries run per sequence.  The per-chunk and per-token
+// arithmetic is the dense code, so a sequence's outputs have the bits of a dense run on it alone.
 // No atomics: dB / dC (sums over channels) and dA_log / dD / ddt_bias (sums over tokens) are
 // per-workgroup partials summed in a fixed order by a second kernel; bitwise reproducible.
 #include <algorithm>
@@ -74,6 +80,7 @@ struct ConvArgs {
   const bf16_t* du2; long ld_du2;  // a second gradient of u, summed in fp32 (nullable)
   bf16_t* dx; long ld_dx;
   float* partials;             // [nb][5][C]
+  const int* pos;              // varlen: [L] positions inside the sequences (B = 1, L = T)
 };
 
 // c = bf16(Σ_k w[k] * x[l-3+k] + bias); the window slot of position p is p & 3, `i` = l & 3
@@ -88,19 +95,31 @@ __device__ __forceinline__ void conv_point(const float (*xr)[8], const float (*w
   }
 }
 
+// VAR: a row before the strip is loaded only if it lies in the sequence of the strip's first row
+template <bool VAR>
 __device__ __forceinline__ void conv_window(const ConvArgs& a, long row0, int s0, int g,
                                             float (*xr)[8]) {
+  const int reach = VAR ? a.pos[row0 + s0] : 0;
 #pragma unroll
   for (int p = 1; p < 4; ++p) {  // positions s0-4+p; s0 % 4 == 0, so their slots are p
     const int l = s0 - 4 + p;
 #pragma unroll
     for (int e = 0; e < 8; ++e) xr[p][e] = 0.f;
-    if (l >= 0) unpack8(*(const uint4*)(a.x + (row0 + l) * a.ld_x + g * 8), xr[p]);
+    if (l >= 0 && (!VAR || reach >= 4 - p)) unpack8(*(const uint4*)(a.x + (row0 + l) * a.ld_x + g * 8), xr[p]);
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) xr[0][e] = 0.f;
 }
 
+// VAR: row l (slot i) starts a sequence — the three older rows of the window are not its taps
+__device__ __forceinline__ void conv_restart(float (*xr)[8], int i) {
+#pragma unroll
+  for (int d = 1; d < 4; ++d)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) xr[(i + d) & 3][e] = 0.f;
+}
+
+template <bool VAR>
 __global__ __launch_bounds__(256) void causal_conv_fwd_kernel(const ConvArgs a) {
   const int gl = threadIdx.x & 31, slot = threadIdx.x >> 5;
   const int g = blockIdx.x * 32 + gl;
@@ -113,13 +132,14 @@ __global__ __launch_bounds__(256) void causal_conv_fwd_kernel(const ConvArgs a) 
     const int b = (int)(s / a.spl), s0 = (int)(s - (long)b * a.spl) * CV_S;
     const long row0 = (long)b * a.L;
     float xr[4][8];
-    conv_window(a, row0, s0, g, xr);
+    conv_window<VAR>(a, row0, s0, g, xr);
 #pragma unroll 1
     for (int j = 0; j < CV_S; j += 4) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int l = s0 + j + i;
         if (l < a.L) {
+          if (VAR && a.pos[row0 + l] == 0) conv_restart(xr, i);
           unpack8(*(const uint4*)(a.x + (row0 + l) * a.ld_x + g * 8), xr[i]);
           float c[8];
           conv_point(xr, wf, bf, i, c);
@@ -147,6 +167,7 @@ __device__ __forceinline__ void slot_sum(float (*red)[32][8], int slot, int gl, 
     }
 }
 
+template <bool VAR>
 __global__ __launch_bounds__(256) void causal_conv_bwd_kernel(const ConvArgs a) {
   __shared__ float red[CV_SLOTS][32][8];
   const int gl = threadIdx.x & 31, slot = threadIdx.x >> 5;
@@ -167,9 +188,12 @@ __global__ __launch_bounds__(256) void causal_conv_bwd_kernel(const ConvArgs a) 
       const int b = (int)(s / a.spl), s0 = (int)(s - (long)b * a.spl) * CV_S;
       const long row0 = (long)b * a.L;
       float xr[4][8], dcw[4][8];
-      conv_window(a, row0, s0, g, xr);
+      int pw[4] = {0, 0, 0, 0};  // VAR: the positions of the rows whose dc is in the window
+      conv_window<VAR>(a, row0, s0, g, xr);
       // dx[t] = Σ_k w[k] * dc[t+3-k] needs dc up to t+3: the walk runs 3 positions past the strip
-      // (inside the sequence), and only the strip's own positions feed dw / db
+      // (inside the sequence), and only the strip's own positions feed dw / db.  VAR: dc[t+j]
+      // is a tap of dx[t] iff pos[t+j] >= j; a row past the strip that is no tap of the strip's
+      // last row is in another sequence and is not loaded.
 #pragma unroll 1
       for (int j = 0; j < CV_S + 4; j += 4) {
 #pragma unroll
@@ -177,7 +201,13 @@ __global__ __launch_bounds__(256) void causal_conv_bwd_kernel(const ConvArgs a) 
           const int l = s0 + j + i;
 #pragma unroll
           for (int e = 0; e < 8; ++e) dcw[i][e] = 0.f;
-          if (l < a.L && j + i < CV_S + 3) {
+          bool on = l < a.L && j + i < CV_S + 3;
+          if (VAR) {
+            pw[i] = on ? a.pos[row0 + l] : 0;
+            if (j >= CV_S && pw[i] <= j + i - CV_S) on = false;
+            if (on && pw[i] == 0) conv_restart(xr, i);
+          }
+          if (on) {
             unpack8(*(const uint4*)(a.x + (row0 + l) * a.ld_x + g * 8), xr[i]);
             float c[8], d[8];
             conv_point(xr, wf, bf, i, c);
@@ -207,7 +237,10 @@ __global__ __launch_bounds__(256) void causal_conv_bwd_kernel(const ConvArgs a) 
             for (int e = 0; e < 8; ++e) {
               float v = 0.f;
 #pragma unroll
-              for (int k = 0; k < 4; ++k) v = fmaf(wf[k][e], dcw[(i - k) & 3][e], v);
+              for (int k = 0; k < 4; ++k) {
+                const bool tap = !VAR || k == 3 || pw[(i - k) & 3] >= 3 - k;
+                v = fmaf(wf[k][e], tap ? dcw[(i - k) & 3][e] : 0.f, v);
+              }
               o[e] = v;
             }
             *(uint4*)(a.dx + (row0 + t) * a.ld_dx + g * 8) = pack8(o);
@@ -259,7 +292,52 @@ struct ScanArgs {
   float* pbc;                  // [cblocks][B*L][2N]
   float* pch;                  // [B*chunks][N+2][I]
   float* dA_log; float* dD; float* ddt_bias;
+  long rows;                   // B * L, or T
+  // varlen: chunk c of sequence s is chunk cu_chunks[s] + c of `total`; B = n_seq
+  const int* cu_seqlens; const int* cu_chunks;
+  int total;
 };
+
+// The chunk a workgroup works on: the k-th of its sequence's nk, `len` tokens from row `row0`,
+// the gc-th of all (the index of its states / Σδ / partials).
+struct Chunk {
+  int k, nk, len;
+  long gc, row0;
+};
+
+// Dense: grid (channel blocks, chunks [- kofs], B).  VAR: grid (channel blocks, y, z) over the
+// `total` chunks of all sequences; the sequence is found by a binary search over cu_chunks, the
+// same for every lane (scalar loads).  False: no chunk for this workgroup.  The bounds taken from
+// the tables are clamped to the buffers' rows, so a bad table cannot send an access outside them.
+template <bool VAR>
+__device__ __forceinline__ bool scan_chunk_of(const ScanArgs& a, int kofs, Chunk& c) {
+  if (!VAR) {
+    const int b = blockIdx.z;
+    c.k = blockIdx.y + kofs;
+    c.nk = a.chunks;
+    const int t0 = c.k * SC_CH;
+    c.len = min(SC_CH, a.L - t0);
+    c.row0 = (long)b * a.L + t0;
+    c.gc = (long)b * a.chunks + c.k;
+    return true;
+  }
+  const long gc = (long)blockIdx.z * gridDim.y + blockIdx.y;
+  if (gc >= a.total) return false;
+  int lo = 0, hi = a.B;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.cu_chunks[mid] <= gc) lo = mid;
+    else hi = mid;
+  }
+  const int c0 = a.cu_chunks[lo];
+  c.gc = gc;
+  c.k = (int)(gc - c0);
+  c.nk = a.cu_chunks[lo + 1] - c0;
+  c.row0 = (long)a.cu_seqlens[lo] + (long)c.k * SC_CH;
+  const long end = min((long)a.cu_seqlens[lo + 1], a.rows);
+  c.len = (int)min((long)SC_CH, end - c.row0);
+  return c.k >= 0 && c.k < c.nk && c.row0 >= 0 && c.len > 0;
+}
 
 // B (and C) of one chunk as fp32 in LDS; rows at and past `len` are zero, never loaded
 template <int N>
@@ -275,18 +353,20 @@ __device__ __forceinline__ void stage_bc(const bf16_t* src, long ld, long row0, 
 }
 
 // OUT = false: from h = 0, the chunk's end state and Σδ.  OUT = true: from the entry state, y.
-template <int N, bool OUT>
+// (VAR, OUT = false: a sequence's last chunk has no successor to hand a state to)
+template <int N, bool OUT, bool VAR>
 __global__ __launch_bounds__(SC_BLK) void scan_fwd_kernel(const ScanArgs a) {
   __shared__ float sB[SC_CH][N];
   __shared__ float sC[OUT ? SC_CH : 1][N];
-  const int ch = blockIdx.x * SC_BLK + threadIdx.x, k = blockIdx.y, b = blockIdx.z;
-  const int t0 = k * SC_CH, len = min(SC_CH, a.L - t0);
-  const long row0 = (long)b * a.L + t0;
+  Chunk c;
+  if (!scan_chunk_of<VAR>(a, 0, c) || (VAR && !OUT && c.k == c.nk - 1)) return;
+  const int ch = blockIdx.x * SC_BLK + threadIdx.x, k = c.k, len = c.len;
+  const long row0 = c.row0;
   stage_bc<N>(a.Bm, a.ld_bc, row0, len, sB);
   if (OUT) stage_bc<N>(a.Cm, a.ld_bc, row0, len, sC);
   __syncthreads();
   if (ch >= a.I) return;
-  const long so = (((long)b * a.chunks + k) * a.I + ch) * N;
+  const long so = (c.gc * a.I + ch) * N;
   float an[N], h[N];
 #pragma unroll
   for (int n = 0; n < N; ++n) {
@@ -317,7 +397,7 @@ __global__ __launch_bounds__(SC_BLK) void scan_fwd_kernel(const ScanArgs a) {
 #pragma unroll
     for (int n = 0; n < N; n += 4)
       *(float4*)(a.states + so + n) = make_float4(h[n], h[n + 1], h[n + 2], h[n + 3]);
-    a.sumd[((long)b * a.chunks + k) * a.I + ch] = (float)sd;
+    a.sumd[c.gc * a.I + ch] = (float)sd;
   }
 }
 
@@ -325,36 +405,47 @@ __global__ __launch_bounds__(SC_BLK) void scan_fwd_kernel(const ScanArgs a) {
 // of chunk k: E_0 = 0, E_{k+1} = exp(a Σδ_k) E_k + S_k.  REV: the adjoint, backwards —
 // st[k] holds the local entry adjoint of chunk k (k >= 1); afterwards st[k] is the adjoint
 // entering chunk k's end: M_last = 0, M_{k-1} = exp(a Σδ_k) M_k + G_k.
-template <bool REV>
+// VAR: b is a sequence, its chunks are cu_chunks[b] .. cu_chunks[b+1] of `total`: every carry
+// starts from zero at a sequence's start (REV: end) and stops at its end.
+template <bool REV, bool VAR>
 __global__ __launch_bounds__(256) void scan_carry_kernel(int B, int I, int N, int chunks,
                                                          const float* __restrict__ A_log,
                                                          const float* __restrict__ sumd,
-                                                         float* st) {
+                                                         float* st, const int* cu_chunks,
+                                                         int total) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)B * I * N) return;
   const int n = (int)(i % N);
   const long bc = i / N;
   const int ch = (int)(bc % I), b = (int)(bc / I);
+  long base = (long)b * chunks;
+  if (VAR) {
+    base = cu_chunks[b];
+    chunks = min(cu_chunks[b + 1], total) - (int)base;
+    if (base < 0 || chunks < 1) return;
+  }
   const float an = -expf(A_log[(long)ch * N + n]);
   float carry = 0.f;
   for (int j = 0; j < chunks - 1; ++j) {
     const int k = REV ? chunks - 1 - j : j;
-    const long o = ((long)b * chunks + k) * I + ch;
+    const long o = (base + k) * I + ch;
     const float s = st[o * N + n];
     st[o * N + n] = carry;
     carry = fmaf(expf(an * sumd[o]), carry, s);
   }
-  st[(((long)b * chunks + (REV ? 0 : chunks - 1)) * I + ch) * N + n] = carry;
+  st[((base + (REV ? 0 : chunks - 1)) * I + ch) * N + n] = carry;
 }
 
 // The local entry adjoint of a chunk: G_n = Σ_t (Π_{s<=t} α_s) dp_t C_{t,n}, dp = dy silu(z),
 // walked from the chunk's end; and Σδ.
-template <int N>
+// (Chunks 1 .. nk-1 of a sequence: its first chunk has no predecessor to hand an adjoint to.)
+template <int N, bool VAR>
 __global__ __launch_bounds__(SC_BLK) void scan_bwd_local_kernel(const ScanArgs a) {
   __shared__ float sC[SC_CH][N];
-  const int ch = blockIdx.x * SC_BLK + threadIdx.x, k = blockIdx.y + 1, b = blockIdx.z;
-  const int t0 = k * SC_CH, len = min(SC_CH, a.L - t0);
-  const long row0 = (long)b * a.L + t0;
+  Chunk c;
+  if (!scan_chunk_of<VAR>(a, 1, c) || (VAR && c.k == 0)) return;
+  const int ch = blockIdx.x * SC_BLK + threadIdx.x, len = c.len;
+  const long row0 = c.row0;
   stage_bc<N>(a.Cm, a.ld_bc, row0, len, sC);
   __syncthreads();
   if (ch >= a.I) return;
@@ -374,7 +465,7 @@ __global__ __launch_bounds__(SC_BLK) void scan_bwd_local_kernel(const ScanArgs a
     for (int n = 0; n < N; ++n) gq[n] = expf(dl * an[n]) * fmaf(dp, sC[t][n], gq[n]);
     sd += (double)dl;
   }
-  const long o = ((long)b * a.chunks + k) * a.I + ch;
+  const long o = c.gc * a.I + ch;
 #pragma unroll
   for (int n = 0; n < N; n += 4)
     *(float4*)(a.dstates + o * N + n) = make_float4(gq[n], gq[n + 1], gq[n + 2], gq[n + 3]);
@@ -387,17 +478,18 @@ __global__ __launch_bounds__(SC_BLK) void scan_bwd_local_kernel(const ScanArgs a
 // forward from the entry state into hs[], then walk back with μ_t = dp_t C_t + α_{t+1} μ_{t+1}.
 // The per-channel terms of dB / dC go through an LDS tile and are summed over the workgroup's
 // channels in channel order.
-template <int N>
+template <int N, bool VAR>
 __global__ __launch_bounds__(SC_BLK) void scan_bwd_kernel(const ScanArgs a) {
   __shared__ float sB[SC_CH][N];
   __shared__ float sC[SC_CH][N];
   __shared__ float tB[SC_CH][SC_BLK + 1];
   __shared__ float tC[SC_CH][SC_BLK + 1];
+  Chunk c;
+  if (!scan_chunk_of<VAR>(a, 0, c)) return;
   const int tid = threadIdx.x;
-  const int ch = blockIdx.x * SC_BLK + tid, k = blockIdx.y, b = blockIdx.z;
+  const int ch = blockIdx.x * SC_BLK + tid, k = c.k, len = c.len;
   const bool live = ch < a.I;
-  const int t0 = k * SC_CH, len = min(SC_CH, a.L - t0);
-  const long row0 = (long)b * a.L + t0;
+  const long row0 = c.row0;
   stage_bc<N>(a.Bm, a.ld_bc, row0, len, sB);
   stage_bc<N>(a.Cm, a.ld_bc, row0, len, sC);
   float dl[SC_CH], dlu[SC_CH], dpv[SC_CH], q[SC_CH], e[SC_CH], p[SC_CH], hs[SC_CH];
@@ -413,8 +505,8 @@ __global__ __launch_bounds__(SC_BLK) void scan_bwd_kernel(const ScanArgs a) {
     }
   }
   __syncthreads();
-  const long so = (((long)b * a.chunks + k) * a.I + ch) * N;
-  float* pch = a.pch + ((long)b * a.chunks + k) * (N + 2) * a.I;
+  const long so = (c.gc * a.I + ch) * N;
+  float* pch = a.pch + c.gc * (N + 2) * a.I;
 #pragma unroll 1
   for (int n = 0; n < N; ++n) {
     const float an = live ? -expf(a.A_log[(long)ch * N + n]) : 0.f;
@@ -427,7 +519,7 @@ __global__ __launch_bounds__(SC_BLK) void scan_bwd_kernel(const ScanArgs a) {
       p[t] = fmaf(sC[t][n], h, p[t]);
       tC[t][tid] = dpv[t] * h;
     }
-    float lam = (live && k < a.chunks - 1) ? a.dstates[so + n] : 0.f;
+    float lam = (live && k < c.nk - 1) ? a.dstates[so + n] : 0.f;
     float da = 0.f;
 #pragma unroll
     for (int t = SC_CH - 1; t >= 0; --t) {
@@ -449,7 +541,7 @@ __global__ __launch_bounds__(SC_BLK) void scan_bwd_kernel(const ScanArgs a) {
       float s = 0.f;
       for (int i = 0; i < SC_BLK; ++i) s += src[i];
       if (t < len)
-        a.pbc[((long)blockIdx.x * a.B * a.L + row0 + t) * (2 * N) + (tid < SC_CH ? 0 : N) + n] = s;
+        a.pbc[((long)blockIdx.x * a.rows + row0 + t) * (2 * N) + (tid < SC_CH ? 0 : N) + n] = s;
     }
     __syncthreads();
   }
@@ -532,6 +624,68 @@ inline bool scan_shape_ok(int64_t B, int64_t L, int64_t I, int64_t N) {
 inline int64_t scan_chunks(int64_t L) { return (L + SC_CH - 1) / SC_CH; }
 inline int64_t scan_cblocks(int64_t I) { return (I + SC_BLK - 1) / SC_BLK; }
 
+// Varlen: T tokens in n_seq sequences of at least one token, `total` chunks in all
+// (Σ ceil(len / chunk), which the tables on the device must agree with).
+inline bool scan_varlen_ok(int64_t T, int64_t n_seq, int64_t total, int64_t I, int64_t N) {
+  return n_seq > 0 && n_seq <= 65535 && T >= n_seq && T < ((int64_t)1 << 31) && I > 0 &&
+         I % 8 == 0 && I < ((int64_t)1 << 24) && (N == 8 || N == 16) &&
+         total >= std::max(n_seq, scan_chunks(T)) && total <= std::min(T, T / SC_CH + n_seq);
+}
+
+// The launch sequences, dense (grid y = chunks, z = B) and varlen (y, z over all chunks).  nseq:
+// the sequences the carries run over; nch: every chunk; multi: some sequence has two chunks.
+template <bool VAR>
+inline dim3 scan_grid(const ScanArgs& a, int drop) {
+  if (!VAR) return dim3((unsigned)a.cblocks, (unsigned)(a.chunks - drop), (unsigned)a.B);
+  const unsigned gy = (unsigned)std::min(a.total, 65535);
+  return dim3((unsigned)a.cblocks, gy, (unsigned)((a.total + gy - 1) / gy));
+}
+
+template <bool VAR>
+int scan_fwd_launch(const ScanArgs& a, const char* what, hipStream_t s) {
+  const bool multi = VAR ? a.total > a.B : a.chunks > 1;
+  int rc;
+  if (multi) {
+    const dim3 lgrid = scan_grid<VAR>(a, 1);
+    if (a.N == 16) scan_fwd_kernel<16, false, VAR><<<lgrid, SC_BLK, 0, s>>>(a);
+    else scan_fwd_kernel<8, false, VAR><<<lgrid, SC_BLK, 0, s>>>(a);
+    if ((rc = check_launch(what))) return rc;
+    scan_carry_kernel<false, VAR><<<(unsigned)(((int64_t)a.B * a.I * a.N + 255) / 256), 256, 0, s>>>(
+        a.B, a.I, a.N, a.chunks, a.A_log, a.sumd, a.states, a.cu_chunks, a.total);
+    if ((rc = check_launch(what))) return rc;
+  }
+  const dim3 grid = scan_grid<VAR>(a, 0);
+  if (a.N == 16) scan_fwd_kernel<16, true, VAR><<<grid, SC_BLK, 0, s>>>(a);
+  else scan_fwd_kernel<8, true, VAR><<<grid, SC_BLK, 0, s>>>(a);
+  return check_launch(what);
+}
+
+template <bool VAR>
+int scan_bwd_launch(const ScanArgs& a, const char* what, hipStream_t s) {
+  const bool multi = VAR ? a.total > a.B : a.chunks > 1;
+  const int64_t nch = VAR ? a.total : (int64_t)a.B * a.chunks;
+  int rc;
+  if (multi) {
+    const dim3 lgrid = scan_grid<VAR>(a, 1);
+    if (a.N == 16) scan_bwd_local_kernel<16, VAR><<<lgrid, SC_BLK, 0, s>>>(a);
+    else scan_bwd_local_kernel<8, VAR><<<lgrid, SC_BLK, 0, s>>>(a);
+    if ((rc = check_launch(what))) return rc;
+    scan_carry_kernel<true, VAR><<<(unsigned)(((int64_t)a.B * a.I * a.N + 255) / 256), 256, 0, s>>>(
+        a.B, a.I, a.N, a.chunks, a.A_log, a.sumd, a.dstates, a.cu_chunks, a.total);
+    if ((rc = check_launch(what))) return rc;
+  }
+  const dim3 grid = scan_grid<VAR>(a, 0);
+  if (a.N == 16) scan_bwd_kernel<16, VAR><<<grid, SC_BLK, 0, s>>>(a);
+  else scan_bwd_kernel<8, VAR><<<grid, SC_BLK, 0, s>>>(a);
+  if ((rc = check_launch(what))) return rc;
+  scan_reduce_bc_kernel<<<(unsigned)((a.rows * 2 * a.N + 255) / 256), 256, 0, s>>>(
+      a.rows, a.N, a.cblocks, a.pbc, a.dB, a.dC, a.ld_dbc);
+  if ((rc = check_launch(what))) return rc;
+  scan_reduce_ch_kernel<<<(unsigned)(((a.N + 2) * (int64_t)a.I + 255) / 256), 256, 0, s>>>(
+      a.I, a.N, (int)nch, a.pch, a.dA_log, a.dD, a.ddt_bias);
+  return check_launch(what);
+}
+
 }  // namespace
 }  // namespace mmpt
 
@@ -542,8 +696,6 @@ using namespace mmpt;
                what ": B, L >= 1 with B*L < 2^31, C a positive multiple of 8 and <= 65536 "     \
                     "(B %lld, L %lld, C %lld)", (long long)B, (long long)L, (long long)C);       \
   MMPT_REQUIRE(K == 4, what ": K must be 4 (K %lld)", (long long)K)
-#define MMPT_MB_LD(what, ld, n) \
-  MMPT_REQUIRE((ld) >= (n) && (ld) % 8 == 0, what ": " #ld " must be a multiple of 8 and >= " #n)
 #define MMPT_MB_SCAN(what)                                                                        \
   MMPT_REQUIRE(scan_shape_ok(B, L, I, N),                                                         \
                what ": B in [1, 65535], L >= 1 with B*L < 2^31 and at most 65535 chunks, I a "   \
@@ -552,22 +704,44 @@ using namespace mmpt;
 
 extern "C" int64_t mmpt_selective_scan_chunk(void) { return SC_CH; }
 
+// The dense entries and the varlen ones (pos != nullptr: B = 1, L = T) share everything below
+// their argument lists.
+#define MMPT_MB_POS(what)                                                                        \
+  MMPT_REQUIRE(pos != nullptr && al4(pos), what ": pos must be a 4-byte aligned int32 [T] table")
+
+static int conv_fwd(const char* what, int64_t B, int64_t L, int64_t C, const void* pos,
+                    const void* x, int64_t ld_x, const void* w, const void* bias, void* u,
+                    int64_t ld_u, void* stream) {
+  MMPT_REQUIRE(ld_x >= C && ld_x % 8 == 0 && ld_u >= C && ld_u % 8 == 0,
+               "%s: ld_x and ld_u must be multiples of 8 and >= C", what);
+  MMPT_REQUIRE(x && w && bias && u, "%s: null pointer", what);
+  MMPT_REQUIRE(al16(x) && al16(w) && al16(bias) && al16(u),
+               "%s: pointers must be 16-byte aligned", what);
+  ConvArgs a = {};
+  conv_geometry(a, B, L, C);
+  a.x = (const bf16_t*)x; a.ld_x = ld_x; a.w = (const bf16_t*)w; a.bias = (const bf16_t*)bias;
+  a.u = (bf16_t*)u; a.ld_u = ld_u; a.pos = (const int*)pos;
+  const dim3 grid((unsigned)((a.G + 31) / 32), (unsigned)conv_nb(a, 65535));
+  if (pos) causal_conv_fwd_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  else causal_conv_fwd_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  return check_launch(what);
+}
+
 extern "C" int mmpt_causal_conv1d_fwd(int64_t B, int64_t L, int64_t C, int64_t K, const void* x,
                                       int64_t ld_x, const void* w, const void* bias, void* u,
                                       int64_t ld_u, void* stream) {
   MMPT_MB_CONV("causal_conv1d_fwd");
-  MMPT_MB_LD("causal_conv1d_fwd", ld_x, C);
-  MMPT_MB_LD("causal_conv1d_fwd", ld_u, C);
-  MMPT_REQUIRE(x && w && bias && u, "causal_conv1d_fwd: null pointer");
-  MMPT_REQUIRE(al16(x) && al16(w) && al16(bias) && al16(u),
-               "causal_conv1d_fwd: pointers must be 16-byte aligned");
-  ConvArgs a = {};
-  conv_geometry(a, B, L, C);
-  a.x = (const bf16_t*)x; a.ld_x = ld_x; a.w = (const bf16_t*)w; a.bias = (const bf16_t*)bias;
-  a.u = (bf16_t*)u; a.ld_u = ld_u;
-  const dim3 grid((unsigned)((a.G + 31) / 32), (unsigned)conv_nb(a, 65535));
-  causal_conv_fwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
-  return check_launch("causal_conv1d_fwd");
+  return conv_fwd("causal_conv1d_fwd", B, L, C, nullptr, x, ld_x, w, bias, u, ld_u, stream);
+}
+
+extern "C" int mmpt_causal_conv1d_varlen_fwd(int64_t T, int64_t C, int64_t K, const void* pos,
+                                             const void* x, int64_t ld_x, const void* w,
+                                             const void* bias, void* u, int64_t ld_u,
+                                             void* stream) {
+  const int64_t B = 1, L = T;
+  MMPT_MB_CONV("causal_conv1d_varlen_fwd");
+  MMPT_MB_POS("causal_conv1d_varlen_fwd");
+  return conv_fwd("causal_conv1d_varlen_fwd", B, L, C, pos, x, ld_x, w, bias, u, ld_u, stream);
 }
 
 extern "C" int64_t mmpt_causal_conv1d_bwd_workspace_bytes(int64_t B, int64_t L, int64_t C) {
@@ -577,36 +751,59 @@ extern "C" int64_t mmpt_causal_conv1d_bwd_workspace_bytes(int64_t B, int64_t L, 
   return conv_nb(a, CV_BLOCKS) * 5 * C * (int64_t)sizeof(float);
 }
 
+static int conv_bwd(const char* what, int64_t B, int64_t L, int64_t C, const void* pos,
+                    const void* x, int64_t ld_x, const void* w, const void* bias, const void* du,
+                    int64_t ld_du, const void* du2, int64_t ld_du2, void* dx, int64_t ld_dx,
+                    float* dw, float* db, void* workspace, void* stream) {
+  MMPT_REQUIRE(ld_x >= C && ld_x % 8 == 0 && ld_du >= C && ld_du % 8 == 0 && ld_dx >= C &&
+                   ld_dx % 8 == 0 && (du2 == nullptr || (ld_du2 >= C && ld_du2 % 8 == 0)),
+               "%s: ld_x, ld_du, ld_du2 and ld_dx must be multiples of 8 and >= C", what);
+  MMPT_REQUIRE(x && w && bias && du && dx && dw && db && workspace, "%s: null pointer", what);
+  MMPT_REQUIRE(al16(x) && al16(w) && al16(bias) && al16(du) && al16(du2) && al16(dx) && al16(dw) &&
+                   al16(db) && al16(workspace),
+               "%s: pointers must be 16-byte aligned", what);
+  ConvArgs a = {};
+  conv_geometry(a, B, L, C);
+  a.x = (const bf16_t*)x; a.ld_x = ld_x; a.w = (const bf16_t*)w; a.bias = (const bf16_t*)bias;
+  a.du = (const bf16_t*)du; a.ld_du = ld_du; a.du2 = (const bf16_t*)du2; a.ld_du2 = ld_du2;
+  a.dx = (bf16_t*)dx; a.ld_dx = ld_dx;
+  a.partials = (float*)workspace; a.pos = (const int*)pos;
+  const int nb = (int)conv_nb(a, CV_BLOCKS);
+  const dim3 grid((unsigned)((a.G + 31) / 32), (unsigned)nb);
+  if (pos) causal_conv_bwd_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  else causal_conv_bwd_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  int rc = check_launch(what);
+  if (rc) return rc;
+  causal_conv_reduce_kernel<<<(unsigned)((5 * C + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      (int)C, nb, a.partials, dw, db);
+  return check_launch(what);
+}
+
 extern "C" int mmpt_causal_conv1d_bwd(int64_t B, int64_t L, int64_t C, int64_t K, const void* x,
                                       int64_t ld_x, const void* w, const void* bias,
                                       const void* du, int64_t ld_du, const void* du2,
                                       int64_t ld_du2, void* dx, int64_t ld_dx, float* dw,
                                       float* db, void* workspace, void* stream) {
   MMPT_MB_CONV("causal_conv1d_bwd");
-  MMPT_MB_LD("causal_conv1d_bwd", ld_x, C);
-  MMPT_MB_LD("causal_conv1d_bwd", ld_du, C);
-  MMPT_MB_LD("causal_conv1d_bwd", ld_dx, C);
-  MMPT_REQUIRE(du2 == nullptr || (ld_du2 >= C && ld_du2 % 8 == 0),
-               "causal_conv1d_bwd: ld_du2 must be a multiple of 8 and >= C");
-  MMPT_REQUIRE(x && w && bias && du && dx && dw && db && workspace,
-               "causal_conv1d_bwd: null pointer");
-  MMPT_REQUIRE(al16(x) && al16(w) && al16(bias) && al16(du) && al16(du2) && al16(dx) && al16(dw) &&
-                   al16(db) && al16(workspace),
-               "causal_conv1d_bwd: pointers must be 16-byte aligned");
-  ConvArgs a = {};
-  conv_geometry(a, B, L, C);
-  a.x = (const bf16_t*)x; a.ld_x = ld_x; a.w = (const bf16_t*)w; a.bias = (const bf16_t*)bias;
-  a.du = (const bf16_t*)du; a.ld_du = ld_du; a.du2 = (const bf16_t*)du2; a.ld_du2 = ld_du2;
-  a.dx = (bf16_t*)dx; a.ld_dx = ld_dx;
-  a.partials = (float*)workspace;
-  const int nb = (int)conv_nb(a, CV_BLOCKS);
-  const dim3 grid((unsigned)((a.G + 31) / 32), (unsigned)nb);
-  causal_conv_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
-  int rc = check_launch("causal_conv1d_bwd");
-  if (rc) return rc;
-  causal_conv_reduce_kernel<<<(unsigned)((5 * C + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      (int)C, nb, a.partials, dw, db);
-  return check_launch("causal_conv1d_bwd");
+  return conv_bwd("causal_conv1d_bwd", B, L, C, nullptr, x, ld_x, w, bias, du, ld_du, du2, ld_du2,
+                  dx, ld_dx, dw, db, workspace, stream);
+}
+
+extern "C" int64_t mmpt_causal_conv1d_varlen_bwd_workspace_bytes(int64_t T, int64_t C) {
+  return mmpt_causal_conv1d_bwd_workspace_bytes(1, T, C);
+}
+
+extern "C" int mmpt_causal_conv1d_varlen_bwd(int64_t T, int64_t C, int64_t K, const void* pos,
+                                             const void* x, int64_t ld_x, const void* w,
+                                             const void* bias, const void* du, int64_t ld_du,
+                                             const void* du2, int64_t ld_du2, void* dx,
+                                             int64_t ld_dx, float* dw, float* db, void* workspace,
+                                             void* stream) {
+  const int64_t B = 1, L = T;
+  MMPT_MB_CONV("causal_conv1d_varlen_bwd");
+  MMPT_MB_POS("causal_conv1d_varlen_bwd");
+  return conv_bwd("causal_conv1d_varlen_bwd", B, L, C, pos, x, ld_x, w, bias, du, ld_du, du2,
+                  ld_du2, dx, ld_dx, dw, db, workspace, stream);
 }
 
 extern "C" int64_t mmpt_selective_scan_states_bytes(int64_t B, int64_t L, int64_t I, int64_t N) {
@@ -621,6 +818,57 @@ extern "C" int64_t mmpt_selective_scan_fwd_workspace_bytes(int64_t B, int64_t L,
          mmpt_selective_scan_states_bytes(B, L, I, N);
 }
 
+// The geometry of a scan call: dense (B sequences of L rows, cu_chunks null) or varlen (B = n_seq
+// sequences over `rows` = T rows, `nch` = total chunks, the two device tables).
+struct ScanGeo {
+  int64_t B, L, rows, nch;
+  const void* cu_seqlens;
+  const void* cu_chunks;
+};
+static void scan_geometry(ScanArgs& a, const ScanGeo& g, int64_t I, int64_t N) {
+  a.B = (int)g.B; a.L = (int)g.L; a.I = (int)I; a.N = (int)N;
+  a.chunks = g.cu_chunks ? 0 : (int)scan_chunks(g.L);
+  a.cblocks = (int)scan_cblocks(I);
+  a.rows = g.rows; a.total = (int)g.nch;
+  a.cu_seqlens = (const int*)g.cu_seqlens; a.cu_chunks = (const int*)g.cu_chunks;
+}
+#define MMPT_MB_VARLEN(what)                                                                      \
+  MMPT_REQUIRE(scan_varlen_ok(T, n_seq, total_chunks, I, N),                                      \
+               what ": n_seq in [1, 65535], n_seq <= T < 2^31, total_chunks the sum of "         \
+                    "ceil(len / chunk), I a positive multiple of 8, N 8 or 16 (T %lld, n_seq "   \
+                    "%lld, total_chunks %lld, I %lld, N %lld)", (long long)T, (long long)n_seq,   \
+               (long long)total_chunks, (long long)I, (long long)N);                              \
+  MMPT_REQUIRE(cu_seqlens && cu_chunks && al4(cu_seqlens) && al4(cu_chunks),                      \
+               what ": cu_seqlens and cu_chunks must be 4-byte aligned int32 [n_seq + 1] tables")
+
+static int scan_fwd(const char* what, const ScanGeo& g, int64_t I, int64_t N, const void* u,
+                    int64_t ld_u, const void* dt_raw, int64_t ld_dt, const float* dt_bias,
+                    const float* A_log, const void* Bm, const void* Cm, int64_t ld_bc,
+                    const float* D, const void* z, int64_t ld_z, void* y, int64_t ld_y,
+                    float* states, void* workspace, void* stream) {
+  MMPT_REQUIRE(ld_u >= I && ld_dt >= I && ld_z >= I && ld_y >= I,
+               "%s: ld_u, ld_dt, ld_z, ld_y must be >= I", what);
+  MMPT_REQUIRE(ld_bc >= N && ld_bc % 8 == 0, "%s: ld_bc must be a multiple of 8 and >= N", what);
+  MMPT_REQUIRE(u && dt_raw && dt_bias && A_log && Bm && Cm && D && z && y && workspace,
+               "%s: null pointer", what);
+  MMPT_REQUIRE(al16(Bm) && al16(Cm) && al16(A_log) && al16(states) && al16(workspace) &&
+                   al4(dt_bias) && al4(D),
+               "%s: B, C, A_log, states and the workspace must be 16-byte aligned", what);
+  MMPT_REQUIRE((((uintptr_t)u | (uintptr_t)dt_raw | (uintptr_t)z | (uintptr_t)y) & 1) == 0,
+               "%s: bf16 pointers must be 2-byte aligned", what);
+  ScanArgs a = {};
+  scan_geometry(a, g, I, N);
+  a.u = (const bf16_t*)u; a.ld_u = ld_u; a.dt = (const bf16_t*)dt_raw; a.ld_dt = ld_dt;
+  a.Bm = (const bf16_t*)Bm; a.Cm = (const bf16_t*)Cm; a.ld_bc = ld_bc;
+  a.z = (const bf16_t*)z; a.ld_z = ld_z; a.dt_bias = dt_bias; a.A_log = A_log; a.D = D;
+  a.y = (bf16_t*)y; a.ld_y = ld_y;
+  a.sumd = (float*)workspace;
+  a.states = states ? states
+                    : (float*)((char*)workspace + up64(g.nch * I * (int64_t)sizeof(float)));
+  return g.cu_chunks ? scan_fwd_launch<true>(a, what, (hipStream_t)stream)
+                     : scan_fwd_launch<false>(a, what, (hipStream_t)stream);
+}
+
 extern "C" int mmpt_selective_scan_fwd(int64_t B, int64_t L, int64_t I, int64_t N, const void* u,
                                        int64_t ld_u, const void* dt_raw, int64_t ld_dt,
                                        const float* dt_bias, const float* A_log, const void* Bm,
@@ -628,41 +876,38 @@ extern "C" int mmpt_selective_scan_fwd(int64_t B, int64_t L, int64_t I, int64_t 
                                        const void* z, int64_t ld_z, void* y, int64_t ld_y,
                                        float* states, void* workspace, void* stream) {
   MMPT_MB_SCAN("selective_scan_fwd");
-  MMPT_REQUIRE(ld_u >= I && ld_dt >= I && ld_z >= I && ld_y >= I,
-               "selective_scan_fwd: ld_u, ld_dt, ld_z, ld_y must be >= I");
-  MMPT_MB_LD("selective_scan_fwd", ld_bc, N);
-  MMPT_REQUIRE(u && dt_raw && dt_bias && A_log && Bm && Cm && D && z && y && workspace,
-               "selective_scan_fwd: null pointer");
-  MMPT_REQUIRE(al16(Bm) && al16(Cm) && al16(A_log) && al16(states) && al16(workspace) &&
-                   al4(dt_bias) && al4(D),
-               "selective_scan_fwd: B, C, A_log, states and the workspace must be 16-byte aligned");
-  MMPT_REQUIRE((((uintptr_t)u | (uintptr_t)dt_raw | (uintptr_t)z | (uintptr_t)y) & 1) == 0,
-               "selective_scan_fwd: bf16 pointers must be 2-byte aligned");
-  ScanArgs a = {};
-  a.B = (int)B; a.L = (int)L; a.I = (int)I; a.N = (int)N;
-  a.chunks = (int)scan_chunks(L); a.cblocks = (int)scan_cblocks(I);
-  a.u = (const bf16_t*)u; a.ld_u = ld_u; a.dt = (const bf16_t*)dt_raw; a.ld_dt = ld_dt;
-  a.Bm = (const bf16_t*)Bm; a.Cm = (const bf16_t*)Cm; a.ld_bc = ld_bc;
-  a.z = (const bf16_t*)z; a.ld_z = ld_z; a.dt_bias = dt_bias; a.A_log = A_log; a.D = D;
-  a.y = (bf16_t*)y; a.ld_y = ld_y;
-  a.sumd = (float*)workspace;
-  a.states = states ? states
-                    : (float*)((char*)workspace + up64(B * a.chunks * I * (int64_t)sizeof(float)));
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (a.chunks > 1) {
-    const dim3 lgrid((unsigned)a.cblocks, (unsigned)(a.chunks - 1), (unsigned)B);
-    if (N == 16) scan_fwd_kernel<16, false><<<lgrid, SC_BLK, 0, s>>>(a);
-    else scan_fwd_kernel<8, false><<<lgrid, SC_BLK, 0, s>>>(a);
-    if ((rc = check_launch("selective_scan_fwd"))) return rc;
-    scan_carry_kernel<false><<<(unsigned)((B * I * N + 255) / 256), 256, 0, s>>>(
-        a.B, a.I, a.N, a.chunks, A_log, a.sumd, a.states);
-    if ((rc = check_launch("selective_scan_fwd"))) return rc;
-  }
-  const dim3 grid((unsigned)a.cblocks, (unsigned)a.chunks, (unsigned)B);
-  if (N == 16) scan_fwd_kernel<16, true><<<grid, SC_BLK, 0, s>>>(a);
-  else scan_fwd_kernel<8, true><<<grid, SC_BLK, 0, s>>>(a);
-  return check_launch("selective_scan_fwd");
+  const ScanGeo g = {B, L, B * L, B * scan_chunks(L), nullptr, nullptr};
+  return scan_fwd("selective_scan_fwd", g, I, N, u, ld_u, dt_raw, ld_dt, dt_bias, A_log, Bm, Cm,
+                  ld_bc, D, z, ld_z, y, ld_y, states, workspace, stream);
+}
+
+extern "C" int64_t mmpt_selective_scan_varlen_states_bytes(int64_t total_chunks, int64_t I,
+                                                           int64_t N) {
+  if (total_chunks <= 0 || total_chunks >= ((int64_t)1 << 31) || I <= 0 || I % 8 ||
+      I >= ((int64_t)1 << 24) || (N != 8 && N != 16))
+    return 0;
+  return total_chunks * I * N * (int64_t)sizeof(float);
+}
+
+extern "C" int64_t mmpt_selective_scan_varlen_fwd_workspace_bytes(int64_t total_chunks, int64_t I,
+                                                                  int64_t N) {
+  const int64_t st = mmpt_selective_scan_varlen_states_bytes(total_chunks, I, N);
+  return st ? up64(total_chunks * I * (int64_t)sizeof(float)) + st : 0;
+}
+
+extern "C" int mmpt_selective_scan_varlen_fwd(int64_t T, int64_t n_seq, int64_t total_chunks,
+                                              const void* cu_seqlens, const void* cu_chunks,
+                                              int64_t I, int64_t N, const void* u, int64_t ld_u,
+                                              const void* dt_raw, int64_t ld_dt,
+                                              const float* dt_bias, const float* A_log,
+                                              const void* Bm, const void* Cm, int64_t ld_bc,
+                                              const float* D, const void* z, int64_t ld_z, void* y,
+                                              int64_t ld_y, float* states, void* workspace,
+                                              void* stream) {
+  MMPT_MB_VARLEN("selective_scan_varlen_fwd");
+  const ScanGeo g = {n_seq, 0, T, total_chunks, cu_seqlens, cu_chunks};
+  return scan_fwd("selective_scan_varlen_fwd", g, I, N, u, ld_u, dt_raw, ld_dt, dt_bias, A_log, Bm,
+                  Cm, ld_bc, D, z, ld_z, y, ld_y, states, workspace, stream);
 }
 
 extern "C" int64_t mmpt_selective_scan_bwd_workspace_bytes(int64_t B, int64_t L, int64_t I,
@@ -671,6 +916,51 @@ extern "C" int64_t mmpt_selective_scan_bwd_workspace_bytes(int64_t B, int64_t L,
   const int64_t chunks = scan_chunks(L), f = (int64_t)sizeof(float);
   return up64(B * chunks * I * f) + up64(B * chunks * I * N * f) +
          up64(scan_cblocks(I) * B * L * 2 * N * f) + up64(B * chunks * (N + 2) * I * f);
+}
+
+static int scan_bwd(const char* what, const ScanGeo& g, int64_t I, int64_t N, const void* u,
+                    int64_t ld_u, const void* dt_raw, int64_t ld_dt, const float* dt_bias,
+                    const float* A_log, const void* Bm, const void* Cm, int64_t ld_bc,
+                    const float* D, const void* z, int64_t ld_z, const float* states,
+                    const void* dy, int64_t ld_dy, const void* du_in, int64_t ld_du_in, void* du,
+                    int64_t ld_du, void* dz, int64_t ld_dz, void* ddt_raw, int64_t ld_ddt,
+                    void* dB, void* dC, int64_t ld_dbc, float* dA_log, float* dD, float* ddt_bias,
+                    void* workspace, void* stream) {
+  MMPT_REQUIRE(ld_u >= I && ld_dt >= I && ld_z >= I && ld_dy >= I && ld_du >= I && ld_dz >= I &&
+                   ld_ddt >= I && (du_in == nullptr || ld_du_in >= I),
+               "%s: every channel leading dimension must be >= I", what);
+  MMPT_REQUIRE(ld_bc >= N && ld_bc % 8 == 0, "%s: ld_bc must be a multiple of 8 and >= N", what);
+  MMPT_REQUIRE(ld_dbc >= N, "%s: ld_dbc must be >= N", what);
+  MMPT_REQUIRE(u && dt_raw && dt_bias && A_log && Bm && Cm && D && z && dy && du && dz &&
+                   ddt_raw && dB && dC && dA_log && dD && ddt_bias && workspace,
+               "%s: null pointer", what);
+  MMPT_REQUIRE(g.nch == g.B || states != nullptr,
+               "%s: more than one chunk in a sequence needs the forward's states", what);
+  MMPT_REQUIRE(al16(Bm) && al16(Cm) && al16(A_log) && al16(states) && al16(workspace) &&
+                   al4(dt_bias) && al4(D) && al4(dA_log) && al4(dD) && al4(ddt_bias),
+               "%s: B, C, A_log, states and the workspace must be 16-byte aligned", what);
+  MMPT_REQUIRE((((uintptr_t)u | (uintptr_t)dt_raw | (uintptr_t)z | (uintptr_t)dy |
+                 (uintptr_t)du_in | (uintptr_t)du | (uintptr_t)dz | (uintptr_t)ddt_raw |
+                 (uintptr_t)dB | (uintptr_t)dC) & 1) == 0,
+               "%s: bf16 pointers must be 2-byte aligned", what);
+  ScanArgs a = {};
+  scan_geometry(a, g, I, N);
+  a.u = (const bf16_t*)u; a.ld_u = ld_u; a.dt = (const bf16_t*)dt_raw; a.ld_dt = ld_dt;
+  a.Bm = (const bf16_t*)Bm; a.Cm = (const bf16_t*)Cm; a.ld_bc = ld_bc;
+  a.z = (const bf16_t*)z; a.ld_z = ld_z; a.dt_bias = dt_bias; a.A_log = A_log; a.D = D;
+  a.states = (float*)states;
+  a.dy = (const bf16_t*)dy; a.ld_dy = ld_dy; a.du_in = (const bf16_t*)du_in; a.ld_dui = ld_du_in;
+  a.du = (bf16_t*)du; a.ld_du = ld_du; a.dz = (bf16_t*)dz; a.ld_dz = ld_dz;
+  a.ddt = (bf16_t*)ddt_raw; a.ld_ddt = ld_ddt; a.dB = (bf16_t*)dB; a.dC = (bf16_t*)dC;
+  a.ld_dbc = ld_dbc; a.dA_log = dA_log; a.dD = dD; a.ddt_bias = ddt_bias;
+  const int64_t f = (int64_t)sizeof(float);
+  char* ws = (char*)workspace;
+  a.sumd = (float*)ws; ws += up64(g.nch * I * f);
+  a.dstates = (float*)ws; ws += up64(g.nch * I * N * f);
+  a.pbc = (float*)ws; ws += up64((int64_t)a.cblocks * g.rows * 2 * N * f);
+  a.pch = (float*)ws;
+  return g.cu_chunks ? scan_bwd_launch<true>(a, what, (hipStream_t)stream)
+                     : scan_bwd_launch<false>(a, what, (hipStream_t)stream);
 }
 
 extern "C" int mmpt_selective_scan_bwd(int64_t B, int64_t L, int64_t I, int64_t N, const void* u,
@@ -684,59 +974,38 @@ extern "C" int mmpt_selective_scan_bwd(int64_t B, int64_t L, int64_t I, int64_t 
                                        void* dC, int64_t ld_dbc, float* dA_log, float* dD,
                                        float* ddt_bias, void* workspace, void* stream) {
   MMPT_MB_SCAN("selective_scan_bwd");
-  MMPT_REQUIRE(ld_u >= I && ld_dt >= I && ld_z >= I && ld_dy >= I && ld_du >= I && ld_dz >= I &&
-                   ld_ddt >= I && (du_in == nullptr || ld_du_in >= I),
-               "selective_scan_bwd: every channel leading dimension must be >= I");
-  MMPT_MB_LD("selective_scan_bwd", ld_bc, N);
-  MMPT_REQUIRE(ld_dbc >= N, "selective_scan_bwd: ld_dbc must be >= N");
-  MMPT_REQUIRE(u && dt_raw && dt_bias && A_log && Bm && Cm && D && z && dy && du && dz &&
-                   ddt_raw && dB && dC && dA_log && dD && ddt_bias && workspace,
-               "selective_scan_bwd: null pointer");
-  MMPT_REQUIRE(L <= SC_CH || states != nullptr,
-               "selective_scan_bwd: more than one chunk needs the forward's states");
-  MMPT_REQUIRE(al16(Bm) && al16(Cm) && al16(A_log) && al16(states) && al16(workspace) &&
-                   al4(dt_bias) && al4(D) && al4(dA_log) && al4(dD) && al4(ddt_bias),
-               "selective_scan_bwd: B, C, A_log, states and the workspace must be 16-byte aligned");
-  MMPT_REQUIRE((((uintptr_t)u | (uintptr_t)dt_raw | (uintptr_t)z | (uintptr_t)dy |
-                 (uintptr_t)du_in | (uintptr_t)du | (uintptr_t)dz | (uintptr_t)ddt_raw |
-                 (uintptr_t)dB | (uintptr_t)dC) & 1) == 0,
-               "selective_scan_bwd: bf16 pointers must be 2-byte aligned");
-  ScanArgs a = {};
-  a.B = (int)B; a.L = (int)L; a.I = (int)I; a.N = (int)N;
-  a.chunks = (int)scan_chunks(L); a.cblocks = (int)scan_cblocks(I);
-  a.u = (const bf16_t*)u; a.ld_u = ld_u; a.dt = (const bf16_t*)dt_raw; a.ld_dt = ld_dt;
-  a.Bm = (const bf16_t*)Bm; a.Cm = (const bf16_t*)Cm; a.ld_bc = ld_bc;
-  a.z = (const bf16_t*)z; a.ld_z = ld_z; a.dt_bias = dt_bias; a.A_log = A_log; a.D = D;
-  a.states = (float*)states;
-  a.dy = (const bf16_t*)dy; a.ld_dy = ld_dy; a.du_in = (const bf16_t*)du_in; a.ld_dui = ld_du_in;
-  a.du = (bf16_t*)du; a.ld_du = ld_du; a.dz = (bf16_t*)dz; a.ld_dz = ld_dz;
-  a.ddt = (bf16_t*)ddt_raw; a.ld_ddt = ld_ddt; a.dB = (bf16_t*)dB; a.dC = (bf16_t*)dC;
-  a.ld_dbc = ld_dbc; a.dA_log = dA_log; a.dD = dD; a.ddt_bias = ddt_bias;
+  const ScanGeo g = {B, L, B * L, B * scan_chunks(L), nullptr, nullptr};
+  return scan_bwd("selective_scan_bwd", g, I, N, u, ld_u, dt_raw, ld_dt, dt_bias, A_log, Bm, Cm,
+                  ld_bc, D, z, ld_z, states, dy, ld_dy, du_in, ld_du_in, du, ld_du, dz, ld_dz,
+                  ddt_raw, ld_ddt, dB, dC, ld_dbc, dA_log, dD, ddt_bias, workspace, stream);
+}
+
+extern "C" int64_t mmpt_selective_scan_varlen_bwd_workspace_bytes(int64_t T, int64_t total_chunks,
+                                                                  int64_t I, int64_t N) {
+  if (!mmpt_selective_scan_varlen_states_bytes(total_chunks, I, N) || T < total_chunks ||
+      T >= ((int64_t)1 << 31))
+    return 0;
   const int64_t f = (int64_t)sizeof(float);
-  char* ws = (char*)workspace;
-  a.sumd = (float*)ws; ws += up64(B * a.chunks * I * f);
-  a.dstates = (float*)ws; ws += up64(B * a.chunks * I * N * f);
-  a.pbc = (float*)ws; ws += up64((int64_t)a.cblocks * B * L * 2 * N * f);
-  a.pch = (float*)ws;
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (a.chunks > 1) {
-    const dim3 lgrid((unsigned)a.cblocks, (unsigned)(a.chunks - 1), (unsigned)B);
-    if (N == 16) scan_bwd_local_kernel<16><<<lgrid, SC_BLK, 0, s>>>(a);
-    else scan_bwd_local_kernel<8><<<lgrid, SC_BLK, 0, s>>>(a);
-    if ((rc = check_launch("selective_scan_bwd"))) return rc;
-    scan_carry_kernel<true><<<(unsigned)((B * I * N + 255) / 256), 256, 0, s>>>(
-        a.B, a.I, a.N, a.chunks, A_log, a.sumd, a.dstates);
-    if ((rc = check_launch("selective_scan_bwd"))) return rc;
-  }
-  const dim3 grid((unsigned)a.cblocks, (unsigned)a.chunks, (unsigned)B);
-  if (N == 16) scan_bwd_kernel<16><<<grid, SC_BLK, 0, s>>>(a);
-  else scan_bwd_kernel<8><<<grid, SC_BLK, 0, s>>>(a);
-  if ((rc = check_launch("selective_scan_bwd"))) return rc;
-  scan_reduce_bc_kernel<<<(unsigned)((B * L * 2 * N + 255) / 256), 256, 0, s>>>(
-      B * L, a.N, a.cblocks, a.pbc, a.dB, a.dC, ld_dbc);
-  if ((rc = check_launch("selective_scan_bwd"))) return rc;
-  scan_reduce_ch_kernel<<<(unsigned)(((N + 2) * I + 255) / 256), 256, 0, s>>>(
-      a.I, a.N, (int)(B * a.chunks), a.pch, dA_log, dD, ddt_bias);
-  return check_launch("selective_scan_bwd");
+  return up64(total_chunks * I * f) + up64(total_chunks * I * N * f) +
+         up64(scan_cblocks(I) * T * 2 * N * f) + up64(total_chunks * (N + 2) * I * f);
+}
+
+extern "C" int mmpt_selective_scan_varlen_bwd(int64_t T, int64_t n_seq, int64_t total_chunks,
+                                              const void* cu_seqlens, const void* cu_chunks,
+                                              int64_t I, int64_t N, const void* u, int64_t ld_u,
+                                              const void* dt_raw, int64_t ld_dt,
+                                              const float* dt_bias, const float* A_log,
+                                              const void* Bm, const void* Cm, int64_t ld_bc,
+                                              const float* D, const void* z, int64_t ld_z,
+                                              const float* states, const void* dy, int64_t ld_dy,
+                                              const void* du_in, int64_t ld_du_in, void* du,
+                                              int64_t ld_du, void* dz, int64_t ld_dz,
+                                              void* ddt_raw, int64_t ld_ddt, void* dB, void* dC,
+                                              int64_t ld_dbc, float* dA_log, float* dD,
+                                              float* ddt_bias, void* workspace, void* stream) {
+  MMPT_MB_VARLEN("selective_scan_varlen_bwd");
+  const ScanGeo g = {n_seq, 0, T, total_chunks, cu_seqlens, cu_chunks};
+  return scan_bwd("selective_scan_varlen_bwd", g, I, N, u, ld_u, dt_raw, ld_dt, dt_bias, A_log, Bm,
+                  Cm, ld_bc, D, z, ld_z, states, dy, ld_dy, du_in, ld_du_in, du, ld_du, dz, ld_dz,
+                  ddt_raw, ld_ddt, dB, dC, ld_dbc, dA_log, dD, ddt_bias, workspace, stream);
 }

@@ -16,7 +16,9 @@ unchanged): the number of text tokens of sample `index` is drawn from
 U{min_text_length..full} by a generator of its own seeded from (seed, index), and the sample
 is returned at that length; `pad_collate` right-pads a list of such samples into the batch
 format of the reference's LlavaCollator (src/data/llava_data.py:169-185: input_ids,
-attention_mask with zeros and labels = -100 at the pads, pixel_values).
+attention_mask with zeros and labels = -100 at the pads, pixel_values).  `pack_collate` places
+such samples several to a row of a fixed width instead and marks the documents by `position_ids`
+(the HF packing convention: a 0 starts a document), which engine.Batch keeps apart.
 """
 
 from __future__ import annotations
@@ -55,6 +57,45 @@ def pad_collate(samples: list[dict], pad_token_id: int = 0) -> dict:
     if "pixel_values" in samples[0]:
         out["pixel_values"] = torch.stack([s["pixel_values"] for s in samples])
     return out
+
+
+def pack_collate(samples: list[dict], width: int, pad_token_id: int = 0) -> dict:
+    """Pack samples of unequal length into rows of `width` tokens: the samples are taken in
+    order and each goes into the first row that still has room for it (first fit; a new row when
+    none has).  Returns input_ids (pad_token_id at the trailing pads), labels (-100 at the pads),
+    position_ids (each sample counts from 0; 0 at the pads) and attention_mask (1 / 0).  A sample
+    longer than `width` raises ValueError.  Pairs with
+    DummyTextModelingDataset(min_text_length=...)."""
+    rows: list[list[dict]] = []
+    used: list[int] = []
+    for i, s in enumerate(samples):
+        k = s["input_ids"].numel()
+        if k > width:
+            raise ValueError(f"pack_collate: sample {i} has {k} tokens, more than the row width "
+                             f"{width}")
+        if k == 0:
+            raise ValueError(f"pack_collate: sample {i} is empty")
+        r = next((j for j, u in enumerate(used) if u + k <= width), len(rows))
+        if r == len(rows):
+            rows.append([])
+            used.append(0)
+        rows[r].append(s)
+        used[r] += k
+    n = len(rows)
+    ids = torch.full((n, width), pad_token_id, dtype=torch.int64)
+    labels = torch.full((n, width), -100, dtype=torch.int64)
+    pos = torch.zeros((n, width), dtype=torch.int64)
+    mask = torch.zeros((n, width), dtype=torch.int64)
+    for r, row in enumerate(rows):
+        c = 0
+        for s in row:
+            k = s["input_ids"].numel()
+            ids[r, c:c + k] = s["input_ids"]
+            labels[r, c:c + k] = s["labels"]
+            pos[r, c:c + k] = torch.arange(k)
+            mask[r, c:c + k] = 1
+            c += k
+    return {"input_ids": ids, "labels": labels, "position_ids": pos, "attention_mask": mask}
 
 
 class DummyTextModelingDataset(Dataset):

@@ -141,7 +141,20 @@ class Batch:
     `pos` (int32 [T], the position of each token inside its sequence) carry the geometry to
     the varlen attention and the positional rope; both are None on the dense path (no mask,
     or a mask without zeros), which is then object for object what it was without the
-    argument.  B stays the number of sequences, S the padded width.
+    argument.  B stays the number of rows, S the padded width.
+
+    Packed rows (`position_ids`, int [B, S] in the HF packing convention — what
+    DataCollatorWithFlattening and data.pack_collate yield): inside the valid part of a row every
+    entry is the previous one + 1 or 0, each row starts at 0, and a 0 starts a new document.  The
+    text-only causal LMs take it (GPTNeoX, Llama, Mamba).  When some row restarts after column 0
+    the batch takes the same varlen form with one sequence per DOCUMENT, in row-major order:
+    `lens` / `cu_seqlens` ([n_seq + 1]) / `pos` / `max_len` describe the documents, `n_seq =
+    len(lens)` (B on every other path), and the label shift is done per document — the last token
+    of a document gets no target, so nothing is trained to predict the next document's first
+    token; a one-token document carries no label.  Trailing pads marked by `attention_mask` are
+    dropped as above and `position_ids` under them is ignored.  Without a restart the argument
+    changes nothing.  For Mamba `scan_tables` (kernels.ScanTables: the scan's chunk offsets) is
+    staged with the rest; a padded Mamba batch without `position_ids` stays refused.
 
     Masked-LM batches (TextConfig.arch "roberta"): no label shift — the label of row r is the
     target of row r — and `pos_ids` (int64 [T]): HF's create_position_ids_from_input_ids over the
@@ -157,11 +170,16 @@ class Batch:
 
     def __init__(self, cfg: ModelConfig, input_ids: torch.Tensor | None, labels: torch.Tensor,
                  pixel_values: torch.Tensor | None, device: torch.device, stream=None,
-                 attention_mask: torch.Tensor | None = None):
+                 attention_mask: torch.Tensor | None = None,
+                 position_ids: torch.Tensor | None = None):
         """stream: stage on this (copy) stream instead of the current one — the copies and
         the segment sort then overlap the compute stream's work; `use(stream)` (called by
         Engine.forward) orders the consumer after them."""
         device = torch.device(device)
+        if position_ids is not None and (cfg.classifier or cfg.multimodal or cfg.text.roberta):
+            raise ValueError("position_ids (packed documents) is taken by the text-only causal "
+                             "language models (GPTNeoX, Llama, Mamba), not by multimodal, RoBERTa "
+                             "or classifier configs")
         if cfg.classifier:
             self._init_images(cfg, input_ids, labels, pixel_values, device, stream, attention_mask)
             return
@@ -174,19 +192,22 @@ class Batch:
             raise ValueError("multimodal model needs pixel_values")
         self.T, self.max_len = self.B * self.S, self.S
         self.lens = [self.S] * self.B
-        self.cu_seqlens = self.pos = None
+        self.cu_seqlens = self.pos = self.scan_tables = None
         mask = self._check_mask(attention_mask)
-        if mask is not None and cfg.text.mamba:
-            raise ValueError("arch 'mamba': attention_mask has zeros — padded batches are not "
-                             "built for this model (the scan and the conv run over whole rows)")
+        restart = None if position_ids is None else self._check_positions(position_ids)
+        self.n_seq = len(self.lens)
+        if mask is not None and cfg.text.mamba and position_ids is None:
+            raise ValueError("arch 'mamba': attention_mask has zeros — padded batches are taken "
+                             "with position_ids only (data.pack_collate yields them); without "
+                             "them the scan and the conv run over whole rows")
         self._ready = None
         if stream is not None and device.type == "cuda":
             with torch.cuda.stream(stream):
-                self._stage(cfg, input_ids, labels, pixel_values, device, mask)
+                self._stage(cfg, input_ids, labels, pixel_values, device, mask, restart)
             self._ready = torch.cuda.Event()
             self._ready.record(stream)
         else:
-            self._stage(cfg, input_ids, labels, pixel_values, device, mask)
+            self._stage(cfg, input_ids, labels, pixel_values, device, mask, restart)
 
     def _init_images(self, cfg, input_ids, labels, pixel_values, device, stream, attention_mask):
         v = cfg.vision if cfg.convnext is None else cfg.convnext
@@ -207,7 +228,8 @@ class Batch:
                              "image)")
         self.T, self.max_len = self.B * self.S, self.S
         self.lens = [self.S] * self.B
-        self.cu_seqlens = self.pos = None
+        self.n_seq = self.B
+        self.cu_seqlens = self.pos = self.scan_tables = None
         self._ready = None
         if stream is not None and device.type == "cuda":
             with torch.cuda.stream(stream):
@@ -257,16 +279,55 @@ class Batch:
         self.T, self.max_len = int(lens.sum()), int(lens.max())
         return torch.from_numpy(m)
 
-    def _stage(self, cfg, input_ids, labels, pixel_values, device, mask=None):
+    def _check_positions(self, position_ids):
+        """None when no row restarts after column 0 (the argument then changes nothing); else the
+        host bool [B, S] map of the columns > 0 at which a document starts, with lens / T /
+        max_len set to the documents' (row-major).  The valid part of row b is its first
+        lens[b] columns (the whole row without a padding mask)."""
+        if tuple(position_ids.shape) != (self.B, self.S):
+            raise ValueError(f"position_ids shape {tuple(position_ids.shape)} != input_ids shape "
+                             f"{(self.B, self.S)}")
+        if position_ids.is_floating_point() or position_ids.dtype == torch.bool:
+            raise ValueError(f"position_ids must be an integer tensor, got {position_ids.dtype}")
+        p = position_ids.detach().to("cpu", torch.int64).numpy()
+        restart = np.zeros((self.B, self.S), bool)
+        docs = []
+        for b in range(self.B):
+            n = self.lens[b]
+            r = p[b, :n]
+            if r[0] != 0:
+                raise ValueError(f"position_ids row {b} column 0 is {int(r[0])}: every row starts "
+                                 "at 0")
+            bad = np.flatnonzero((r[1:] != r[:-1] + 1) & (r[1:] != 0))
+            if bad.size:
+                c = int(bad[0]) + 1
+                raise ValueError(f"position_ids row {b} column {c} is {int(r[c])} after "
+                                 f"{int(r[c - 1])}: neither the previous position + 1 nor a "
+                                 "restart at 0")
+            starts = np.flatnonzero(r == 0)
+            restart[b, starts[1:]] = True
+            docs.extend(int(x) for x in np.diff(np.concatenate((starts, [n]))))
+        if not restart.any():
+            return None
+        if len(docs) > 65535:
+            raise ValueError(f"position_ids marks {len(docs)} documents; at most 65535 sequences "
+                             "in a batch")
+        self.lens = docs
+        self.T, self.max_len = sum(docs), max(docs)
+        return torch.from_numpy(restart)
+
+    def _stage(self, cfg, input_ids, labels, pixel_values, device, mask=None, restart=None):
         if input_ids.device.type == "cpu" and labels.device.type == "cpu":
-            self._from_host(cfg, input_ids, labels, device, mask)
+            self._from_host(cfg, input_ids, labels, device, mask, restart)
         else:
-            self._from_device(cfg, input_ids, labels, device, mask)
-        if mask is not None:
+            self._from_device(cfg, input_ids, labels, device, mask, restart)
+        if mask is not None or restart is not None:
             cu = np.concatenate(([0], np.cumsum(self.lens))).astype(np.int32)
             pos = np.concatenate([np.arange(n, dtype=np.int32) for n in self.lens])
             self.cu_seqlens = _to(torch.from_numpy(cu), device, torch.int32)
             self.pos = _to(torch.from_numpy(pos), device, torch.int32)
+            if cfg.text.mamba and device.type == "cuda":  # the varlen scan's chunk offsets
+                self.scan_tables = K.scan_tables(self.lens, device)
         self.pixels = None
         if cfg.multimodal:
             self.pixels = _to(pixel_values, device, F32)
@@ -282,12 +343,14 @@ class Batch:
         stream.wait_event(self._ready)
         for t in (self.ids, self.labels, self.loss_rows, self.loss_labels, self.loss_map,
                   self.img_map, self.pixels, self.cu_seqlens, self.pos, self.pos_ids,
-                  *self.segments, *self.pos_segments):
+                  *self.segments, *self.pos_segments,
+                  *((self.scan_tables.cu_seqlens, self.scan_tables.cu_chunks)
+                    if self.scan_tables is not None else ())):
             if t is not None:
                 t.record_stream(stream)
         self._ready = None
 
-    def _from_host(self, cfg, input_ids, labels, device, mask=None):
+    def _from_host(self, cfg, input_ids, labels, device, mask=None, restart=None):
         ids = input_ids.reshape(-1).to(torch.int64)
         lab = labels.to(torch.int64)
         if mask is not None:  # HF's Llava loss drops the labels under the mask
@@ -298,6 +361,8 @@ class Batch:
         else:
             shifted = torch.full_like(lab, -100)
             shifted[:, :-1] = lab[:, 1:]  # ForCausalLMLoss: pad(labels, (0,1)) then [..., 1:]
+            if restart is not None:  # per document: its last token does not predict the next's first
+                shifted[:, :-1].masked_fill_(restart[:, 1:], -100)
         shifted = shifted.reshape(-1)
         if mask is not None:  # drop the pads: everything below is over the T valid tokens
             sel = mask.reshape(-1)
@@ -337,7 +402,7 @@ class Batch:
             imap = np.where(mask, np.cumsum(mask) - 1, -1).astype(np.int32)
             self.img_map = _to(torch.from_numpy(imap), device, torch.int32)
 
-    def _from_device(self, cfg, input_ids, labels, device, mask=None):
+    def _from_device(self, cfg, input_ids, labels, device, mask=None, restart=None):
         self.ids = input_ids.to(device, torch.int64).contiguous().view(-1)
         sel = None
         if mask is not None:
@@ -361,6 +426,8 @@ class Batch:
         else:
             shifted = torch.full_like(lab, -100)
             shifted[:, :-1] = lab[:, 1:]
+            if restart is not None:
+                shifted[:, :-1].masked_fill_(restart.to(device)[:, 1:], -100)
         self.labels = shifted.contiguous().view(-1)
         if sel is not None:
             self.labels = self.labels[sel].contiguous()
@@ -1588,16 +1655,28 @@ class Engine:
         K.rmsnorm_fwd(x, self.s.p(p + "norm.weight"), t.eps, y, r)
         xz = self._linear(y, p + "in_proj", bias=False)
         u = self._e(T, I)
-        K.causal_conv1d_fwd(xz[:, :I], self.s.w(p + "conv.weight"), self.s.w(p + "conv.bias"), u, S)
+        vl = self._vl  # packed rows: the varlen entries, each sequence on its own
+        if vl is None:
+            K.causal_conv1d_fwd(xz[:, :I], self.s.w(p + "conv.weight"), self.s.w(p + "conv.bias"),
+                                u, S)
+        else:
+            K.causal_conv1d_varlen_fwd(xz[:, :I], self.s.w(p + "conv.weight"),
+                                       self.s.w(p + "conv.bias"), u, vl.pos)
         proj = self._linear(u, p + "x_proj", bias=False)
         dt = self._e(T, I)
         K.gemm(proj[:, :R], self.s.w(p + "dt_proj.weight"), dt)
         ckpt = self.checkpointing and not self._recomputing
-        states = K.scan_states(B, S, I, N, self.dev) if self._scan_keep and not ckpt else None
+        states = None
+        if self._scan_keep and not ckpt:
+            states = K.scan_states(B, S, I, N, self.dev) if vl is None else \
+                K.scan_varlen_states(vl.scan_tables, I, N, self.dev)
         ys = self._e(T, I)
-        K.selective_scan_fwd(u, dt, self.s.p(p + "dt_proj.bias"), self.s.p(p + "A_log"),
-                             proj[:, R:R + N], proj[:, R + N:], self.s.p(p + "D"), xz[:, I:], ys, S,
-                             states=states)
+        scan = (u, dt, self.s.p(p + "dt_proj.bias"), self.s.p(p + "A_log"), proj[:, R:R + N],
+                proj[:, R + N:], self.s.p(p + "D"), xz[:, I:], ys)
+        if vl is None:
+            K.selective_scan_fwd(*scan, S, states=states)
+        else:
+            K.selective_scan_varlen_fwd(*scan, vl.scan_tables, states=states)
         xn = self._linear(ys, p + "out_proj", bias=False, epi=K.EPI_F32_RESID, out2=x)
         if ckpt:
             self.cache[("t", i)] = ("ckpt", x)
@@ -1620,17 +1699,26 @@ class Engine:
         self._dw(ds, ys, p + "out_proj", bias=False)
         dxz, dproj = self._e(T, 2 * I), self._e(T, R + 2 * N)
         du, ddt = self._e(T, I), self._e(T, I)
-        K.selective_scan_bwd(u, dt, self.s.p(p + "dt_proj.bias"), self.s.p(p + "A_log"),
-                             proj[:, R:R + N], proj[:, R + N:], self.s.p(p + "D"), xz[:, I:], dys,
-                             du, dxz[:, I:], ddt, dproj[:, R:R + N], dproj[:, R + N:],
-                             g(p + "A_log"), g(p + "D"), g(p + "dt_proj.bias"), S, states=states)
+        vl = self._vl
+        scan = (u, dt, self.s.p(p + "dt_proj.bias"), self.s.p(p + "A_log"), proj[:, R:R + N],
+                proj[:, R + N:], self.s.p(p + "D"), xz[:, I:], dys, du, dxz[:, I:], ddt,
+                dproj[:, R:R + N], dproj[:, R + N:], g(p + "A_log"), g(p + "D"),
+                g(p + "dt_proj.bias"))
+        if vl is None:
+            K.selective_scan_bwd(*scan, S, states=states)
+        else:
+            K.selective_scan_varlen_bwd(*scan, vl.scan_tables, states=states)
         K.gemm(ddt, self.s.wt(p + "dt_proj.weight"), dproj[:, :R])
         self._dw(ddt, proj[:, :R], p + "dt_proj", bias=False)
         # u feeds the scan and x_proj: the conv's backward sums the two gradients in fp32
         du2 = self._dx(dproj, p + "x_proj")
         self._dw(dproj, u, p + "x_proj", bias=False)
-        K.causal_conv1d_bwd(xz[:, :I], self.s.w(p + "conv.weight"), self.s.w(p + "conv.bias"), du,
-                            dxz[:, :I], g(p + "conv.weight"), g(p + "conv.bias"), S, du2=du2)
+        conv = (xz[:, :I], self.s.w(p + "conv.weight"), self.s.w(p + "conv.bias"), du, dxz[:, :I],
+                g(p + "conv.weight"), g(p + "conv.bias"))
+        if vl is None:
+            K.causal_conv1d_bwd(*conv, S, du2=du2)
+        else:
+            K.causal_conv1d_varlen_bwd(*conv, vl.pos, du2=du2)
         dy = self._dx(dxz, p + "in_proj")
         self._dw(dxz, y, p + "in_proj", bias=False)
         nxt = self._e(T, h) if i > 0 else None
@@ -1643,10 +1731,8 @@ class Engine:
         """MambaForCausalLM: the embedding gather, the blocks, the final RMSNorm, the decoder tied
         to the embedding, Σ CE over the shifted labels.  need_grad = False keeps no scan states."""
         t = self.cfg.text
-        if batch.cu_seqlens is not None:
-            raise ValueError("arch 'mamba': a batch with zeros in attention_mask — padding is not "
-                             "built for this model")
         B, S, T = batch.B, batch.S, batch.T
+        self._vl = batch if batch.cu_seqlens is not None else None
         if self.dev.type == "cuda":
             batch.use(torch.cuda.current_stream(self.dev))
         region = getattr(self.units, "region", None)
@@ -1685,6 +1771,7 @@ class Engine:
         gather's deterministic scatter-add."""
         t = self.cfg.text
         B, S, T = batch.B, batch.S, batch.T
+        self._vl = batch if batch.cu_seqlens is not None else None
         hL, rf, yf, dlogits = self.cache.pop("head")
         if scale is not None:
             dlogits.mul_(scale.to(torch.float32))
@@ -1743,7 +1830,7 @@ class Engine:
         layer_fwd = self._llama_layer_fwd if t.llama else self._text_layer_fwd
         for i in range(t.layers):
             self._unit_fwd(f"text.layers.{i}")
-            h = layer_fwd(i, h, B, S)
+            h = layer_fwd(i, h, batch.n_seq, S)  # (sequences: the documents of packed rows)
         yf = self._e(T, t.hidden)
         mf, rf = self._e(T, dtype=F32), self._e(T, dtype=F32)
         if t.llama:
@@ -1814,7 +1901,7 @@ class Engine:
             layer_bwd = self._text_layer_bwd
         self._ready(("text.final_ln.",) + (() if tied else ("text.lm_head",)))
         for i in reversed(range(t.layers)):
-            dh, ds = layer_bwd(i, dh, ds, B, S)
+            dh, ds = layer_bwd(i, dh, ds, batch.n_seq, S)
             self._ready((f"text.layers.{i}.",))
         dimg = self._e(B * cfg.vision.num_patches, t.hidden) if cfg.multimodal else None
         if self._pt > 0:

@@ -1113,3 +1113,141 @@ def selective_scan_bwd(u, dt_raw, dt_bias, A_log, Bm, Cm, D, z, dy, du, dz, ddt_
               ld_dui, du.data_ptr(), ld_du, dz.data_ptr(), ld_dz, ddt_raw.data_ptr(), ld_ddt,
               dB.data_ptr(), dC.data_ptr(), ld_db, dA_log.data_ptr(), dD.data_ptr(),
               ddt_bias.data_ptr(), ws.data_ptr(), _stream())
+
+
+# Varlen forms: the rows are n_seq sequences laid end to end (a Batch built from position_ids or a
+# padding mask).  The conv takes each token's position inside its sequence; the scan takes the
+# tables of `scan_tables`, built once per batch.
+class ScanTables:
+    """Geometry of a packed batch for the varlen scan: host `lens`, device int32 `cu_seqlens`
+    [n_seq + 1] (row offsets) and `cu_chunks` [n_seq + 1] (chunk offsets: sequence s has
+    ceil(len_s / scan_chunk()) chunks, counted from its own start), T and total_chunks."""
+
+    def __init__(self, lens, device, chunk: int | None = None):
+        ls, total, _ = check_seqlens(lens)
+        if len(ls) > 65535:
+            raise ValueError(f"varlen scan: {len(ls)} sequences; at most 65535")
+        c = scan_chunk() if chunk is None else int(chunk)
+        self.lens, self.n_seq, self.T = ls, len(ls), total
+        cu = torch.zeros(len(ls) + 1, dtype=torch.int64)
+        cu[1:] = torch.tensor(ls, dtype=torch.int64).cumsum(0)
+        cc = torch.zeros(len(ls) + 1, dtype=torch.int64)
+        cc[1:] = torch.tensor([(n + c - 1) // c for n in ls], dtype=torch.int64).cumsum(0)
+        self.total_chunks = int(cc[-1])
+        device = torch.device(device)
+        self.cu_seqlens = cu.to(torch.int32).to(device, non_blocking=True)
+        self.cu_chunks = cc.to(torch.int32).to(device, non_blocking=True)
+
+
+def scan_tables(lens, device) -> ScanTables:
+    """The varlen scan's tables for sequences of `lens` rows (async copies on the current
+    stream; nothing is read back)."""
+    return ScanTables(lens, device)
+
+
+def _pos_table(pos, rows, name) -> None:
+    _check(pos, torch.int32, name)
+    if tuple(pos.shape) != (rows,) or not pos.is_contiguous():
+        raise ValueError(f"{name}: expected a dense int32 [{rows}] tensor, got {tuple(pos.shape)}")
+
+
+def causal_conv1d_varlen_fwd(x, w, bias, u, pos) -> None:
+    """causal_conv1d_fwd over packed rows: pos int32 [T], each token's position inside its
+    sequence; tap t-j is taken iff pos[t] >= j."""
+    name = "causal_conv1d_varlen_fwd"
+    rows, C = x.shape
+    ld_x = _tokens(x, rows, C, name + ".x")
+    ld_u = _tokens(u, rows, C, name + ".u")
+    _dense(w, torch.bfloat16, (4, C), name + ".w")
+    _dense(bias, torch.bfloat16, (C,), name + ".bias")
+    _pos_table(pos, rows, name + ".pos")
+    _lib.call("mmpt_causal_conv1d_varlen_fwd", rows, C, 4, pos.data_ptr(), x.data_ptr(), ld_x,
+              w.data_ptr(), bias.data_ptr(), u.data_ptr(), ld_u, _stream())
+
+
+def causal_conv1d_varlen_bwd(x, w, bias, du, dx, dw, db, pos, du2=None) -> None:
+    """causal_conv1d_bwd over packed rows (pos as in causal_conv1d_varlen_fwd): for dx, tap t+j is
+    taken iff t+j < T and pos[t+j] >= j; dw, db fp32, +=."""
+    name = "causal_conv1d_varlen_bwd"
+    rows, C = x.shape
+    ld_x = _tokens(x, rows, C, name + ".x")
+    ld_du = _tokens(du, rows, C, name + ".du")
+    ld_dx = _tokens(dx, rows, C, name + ".dx")
+    ld_du2 = 0 if du2 is None else _tokens(du2, rows, C, name + ".du2")
+    _dense(w, torch.bfloat16, (4, C), name + ".w")
+    _dense(bias, torch.bfloat16, (C,), name + ".bias")
+    _dense(dw, torch.float32, (4, C), name + ".dw")
+    _dense(db, torch.float32, (C,), name + ".db")
+    _pos_table(pos, rows, name + ".pos")
+    ws = workspace(_lib.query("mmpt_causal_conv1d_varlen_bwd_workspace_bytes", rows, C), slot=2)
+    _lib.call("mmpt_causal_conv1d_varlen_bwd", rows, C, 4, pos.data_ptr(), x.data_ptr(), ld_x,
+              w.data_ptr(), bias.data_ptr(), du.data_ptr(), ld_du, _p(du2), ld_du2, dx.data_ptr(),
+              ld_dx, dw.data_ptr(), db.data_ptr(), ws.data_ptr(), _stream())
+
+
+def scan_varlen_states(tables: ScanTables, I: int, N: int, device) -> torch.Tensor:
+    """An empty tensor for the chunk-entry states of a varlen scan: [total_chunks, I, N]."""
+    return torch.empty(tables.total_chunks, I, N, dtype=torch.float32, device=device)
+
+
+def _scan_varlen_geo(name, tables, rows):
+    if not isinstance(tables, ScanTables):
+        raise TypeError(f"{name}: tables must come from scan_tables()")
+    _check(tables.cu_seqlens, torch.int32, name + ".cu_seqlens")
+    _check(tables.cu_chunks, torch.int32, name + ".cu_chunks")
+    if tables.T != rows:  # the tables' own contents are checked here, on the host copy
+        raise ValueError(f"{name}: cu_seqlens ends at {tables.T}, the operands have {rows} rows")
+    return rows, tables.n_seq, tables.total_chunks, tables.cu_seqlens.data_ptr(), \
+        tables.cu_chunks.data_ptr()
+
+
+def selective_scan_varlen_fwd(u, dt_raw, dt_bias, A_log, Bm, Cm, D, z, y, tables: ScanTables,
+                              states=None) -> None:
+    """selective_scan_fwd over packed rows: every sequence of `tables` starts from h = 0 and its
+    chunks are counted from its own start.  `states` from scan_varlen_states."""
+    name = "selective_scan_varlen_fwd"
+    _, rows, I, N, ld = _scan_operands(name, u, dt_raw, dt_bias, A_log, Bm, Cm, D, z, u.shape[0])
+    geo = _scan_varlen_geo(name, tables, rows)
+    ld_y = _tokens(y, rows, I, name + ".y")
+    if states is not None:
+        _dense(states, torch.float32, (tables.total_chunks, I, N), name + ".states")
+    ws = workspace(_lib.query("mmpt_selective_scan_varlen_fwd_workspace_bytes", geo[2], I, N),
+                   slot=2)
+    _lib.call("mmpt_selective_scan_varlen_fwd", *geo, I, N, u.data_ptr(), ld[0],
+              dt_raw.data_ptr(), ld[1], dt_bias.data_ptr(), A_log.data_ptr(), Bm.data_ptr(),
+              Cm.data_ptr(), ld[2], D.data_ptr(), z.data_ptr(), ld[4], y.data_ptr(), ld_y,
+              _p(states), ws.data_ptr(), _stream())
+
+
+def selective_scan_varlen_bwd(u, dt_raw, dt_bias, A_log, Bm, Cm, D, z, dy, du, dz, ddt_raw, dB, dC,
+                              dA_log, dD, ddt_bias, tables: ScanTables, states=None,
+                              du_in=None) -> None:
+    """selective_scan_bwd over packed rows; `states` is what the varlen forward wrote (needed
+    when a sequence exceeds one chunk)."""
+    name = "selective_scan_varlen_bwd"
+    _, rows, I, N, ld = _scan_operands(name, u, dt_raw, dt_bias, A_log, Bm, Cm, D, z, u.shape[0])
+    geo = _scan_varlen_geo(name, tables, rows)
+    ld_dy = _tokens(dy, rows, I, name + ".dy")
+    ld_du = _tokens(du, rows, I, name + ".du")
+    ld_dz = _tokens(dz, rows, I, name + ".dz")
+    ld_ddt = _tokens(ddt_raw, rows, I, name + ".ddt_raw")
+    ld_db = _tokens(dB, rows, N, name + ".dB")
+    if _tokens(dC, rows, N, name + ".dC") != ld_db:
+        raise ValueError(f"{name}: dB and dC must share a row stride")
+    ld_dui = 0 if du_in is None else _tokens(du_in, rows, I, name + ".du_in")
+    _dense(dA_log, torch.float32, (I, N), name + ".dA_log")
+    _dense(dD, torch.float32, (I,), name + ".dD")
+    _dense(ddt_bias, torch.float32, (I,), name + ".ddt_bias")
+    if states is not None:
+        _dense(states, torch.float32, (tables.total_chunks, I, N), name + ".states")
+    elif tables.total_chunks > tables.n_seq:
+        raise ValueError(f"{name}: a sequence spans several chunks: the forward's states are "
+                         "needed")
+    ws = workspace(_lib.query("mmpt_selective_scan_varlen_bwd_workspace_bytes", rows, geo[2], I,
+                              N), slot=2)
+    _lib.call("mmpt_selective_scan_varlen_bwd", *geo, I, N, u.data_ptr(), ld[0],
+              dt_raw.data_ptr(), ld[1], dt_bias.data_ptr(), A_log.data_ptr(), Bm.data_ptr(),
+              Cm.data_ptr(), ld[2], D.data_ptr(), z.data_ptr(), ld[4], _p(states), dy.data_ptr(),
+              ld_dy, _p(du_in), ld_dui, du.data_ptr(), ld_du, dz.data_ptr(), ld_dz,
+              ddt_raw.data_ptr(), ld_ddt, dB.data_ptr(), dC.data_ptr(), ld_db, dA_log.data_ptr(),
+              dD.data_ptr(), ddt_bias.data_ptr(), ws.data_ptr(), _stream())

@@ -576,7 +576,7 @@ class MMPTForPretraining(nn.Module):
             self._shadow_version = v
 
     def forward(self, input_ids=None, labels=None, pixel_values=None, attention_mask=None,
-                num_items_in_batch=None, **unused):
+                num_items_in_batch=None, position_ids=None, **unused):
         if self.partitioned:
             raise RuntimeError("parameters were partitioned out to a ZeRO-3 trainer "
                                "(partition_out): run the step through that trainer")
@@ -585,9 +585,11 @@ class MMPTForPretraining(nn.Module):
         self._refresh_if_stale()
         self.engine.dropout_enabled = self.training  # eval() switches hidden dropout off
         # a right-padded mask (the reference collators' padding=True) drops the pad tokens:
-        # the step runs over the valid tokens only (Batch); other mask shapes raise ValueError
+        # the step runs over the valid tokens only (Batch); other mask shapes raise ValueError.
+        # position_ids that restart inside a row (HF's DataCollatorWithFlattening) mark packed
+        # documents: attention, rope, the label shift and Mamba's conv / scan stay inside each
         batch = Batch(self.mmpt_config, input_ids, labels, pixel_values, self.store.device,
-                      attention_mask=attention_mask)
+                      attention_mask=attention_mask, position_ids=position_ids)
         denom = float(num_items_in_batch) if num_items_in_batch is not None \
             else float(max(1, batch.num_items))
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._plist):

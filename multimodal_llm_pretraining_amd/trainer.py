@@ -261,9 +261,11 @@ class ManualTrainer:
         """The device side of `_prepare_inputs`: host (ideally pinned) tensors are copied
         asynchronously and the index bookkeeping is built without a device sync; with
         `stream` the staging runs on that copy stream, overlapped with the step.  A right-padded
-        `attention_mask` in the loader's dict drops the pad tokens (Batch)."""
+        `attention_mask` in the loader's dict drops the pad tokens and `position_ids`
+        (data.pack_collate) keeps packed documents apart (Batch)."""
         return Batch(self.cfg, batch.get("input_ids"), batch["labels"], batch.get("pixel_values"),
-                     self.device, stream=stream, attention_mask=batch.get("attention_mask"))
+                     self.device, stream=stream, attention_mask=batch.get("attention_mask"),
+                     position_ids=batch.get("position_ids"))
 
     def manual_training_step(self, batch: Batch, num_items_global: int,
                              last_micro_batch: bool = True) -> torch.Tensor:

@@ -15,7 +15,15 @@ reached by accumulation) at the same micro-batches, plain and with ZeRO-1 + opti
 mfu / executed_mfu against the dense bf16 peak (2.5 PFLOP/s; the two FLOP counts are the same
 number for this family).
 
+With --packed: the four varlen kernels (mmpt_*_varlen_*) on the same operands against the dense
+ones, in one process, alternated: per repeat, each kernel's dense form, its varlen form with equal
+lengths (B sequences of 4096: the same work, so the difference is the cost of the position loads
+and the table search) and its varlen form on a ragged cut of the same T tokens into documents of
+500-4096 tokens drawn from --seed.  Reports the median over --repeats and the repeat-to-repeat
+spread, (max - min) / median, of every figure.
+
 python scripts/bench_mamba.py [--iters 10] [--batches 1,8] [--step] [--ckpt]
+python scripts/bench_mamba.py --packed [--iters 10] [--repeats 5] [--batches 1,8] [--seed 0]
 """
 
 from __future__ import annotations
@@ -50,7 +58,18 @@ def timeit(fn, iters):
     return s.elapsed_time(e) / iters * 1e-3
 
 
-def kernels(B, iters):
+def ragged_lens(T, seed, lo=500, hi=4096):
+    """T tokens cut into documents of lo..hi tokens (the last one takes what is left)."""
+    g = torch.Generator().manual_seed(seed)
+    lens = []
+    while T > 0:
+        n = min(T, int(torch.randint(lo, hi + 1, (1,), generator=g)))
+        lens.append(n)
+        T -= n
+    return lens
+
+
+def kernels(B, iters, packed=False, repeats=5, seed=0):
     t = C.get_config("mamba-2.8b").text
     L, I, N, R = 4096, t.d_inner, t.d_state, t.rank
     T = B * L
@@ -72,6 +91,47 @@ def kernels(B, iters):
         torch.zeros(I, device="cuda")
     states = K.scan_states(B, L, I, N, "cuda")
     Bm, Cm = proj[:, R:R + N], proj[:, R + N:]
+    if packed:
+        scan = (u, dt, dt_bias, A_log, Bm, Cm, D, xz[:, I:])
+        sbwd = scan + (dy, du, dxz[:, I:], ddt, dproj[:, R:R + N], dproj[:, R + N:], dA, dD, dbias)
+        conv = (xz[:, :I], w, bias)
+        cbwd = conv + (du, dxz[:, :I], dw, db)
+        forms = {"dense": {
+            "conv_fwd": lambda: K.causal_conv1d_fwd(*conv, u, L),
+            "scan_fwd": lambda: K.selective_scan_fwd(*scan, y, L, states=states),
+            "scan_bwd": lambda: K.selective_scan_bwd(*sbwd, L, states=states),
+            "conv_bwd": lambda: K.causal_conv1d_bwd(*cbwd, L, du2=dy)}}
+
+        def varlen(lens):
+            tb = K.scan_tables(lens, "cuda")
+            pos = torch.cat([torch.arange(n, dtype=torch.int32) for n in lens]).cuda()
+            st = K.scan_varlen_states(tb, I, N, "cuda")
+            return {"conv_fwd": lambda: K.causal_conv1d_varlen_fwd(*conv, u, pos),
+                    "scan_fwd": lambda: K.selective_scan_varlen_fwd(*scan, y, tb, states=st),
+                    "scan_bwd": lambda: K.selective_scan_varlen_bwd(*sbwd, tb, states=st),
+                    "conv_bwd": lambda: K.causal_conv1d_varlen_bwd(*cbwd, pos, du2=dy)}
+
+        lens = ragged_lens(T, seed)
+        forms["varlen_equal"], forms["varlen_ragged"] = varlen([L] * B), varlen(lens)
+        order = ("conv_fwd", "scan_fwd", "scan_bwd", "conv_bwd")  # (the backwards read the forwards)
+        times = {f: {k: [] for k in order} for f in forms}
+        for _ in range(repeats):
+            for k in order:
+                for f in forms:  # alternated: the forms of one kernel run back to back
+                    times[f][k].append(timeit(forms[f][k], iters))
+        out = {"micro_batch": B, "tokens": T, "repeats": repeats, "ragged_documents": len(lens),
+               "ragged_min_max": [min(lens), max(lens)]}
+        for f in forms:
+            for k in order:
+                v = sorted(times[f][k])
+                med = v[len(v) // 2]
+                out[f"{f}_{k}_us"] = round(med * 1e6, 1)
+                out[f"{f}_{k}_spread"] = round((v[-1] - v[0]) / med, 4)
+        for f in ("varlen_equal", "varlen_ragged"):
+            for k in order:
+                out[f"{f}_{k}_vs_dense"] = round(out[f"{f}_{k}_us"] / out[f"dense_{k}_us"], 4)
+        print(json.dumps(out), flush=True)
+        return
     t_cf = timeit(lambda: K.causal_conv1d_fwd(xz[:, :I], w, bias, u, L), iters)
     t_sf = timeit(lambda: K.selective_scan_fwd(u, dt, dt_bias, A_log, Bm, Cm, D, xz[:, I:], y, L,
                                                states=states), iters)
@@ -118,13 +178,16 @@ def main():
     ap.add_argument("--batches", default="1,8")
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--ckpt", action="store_true")
+    ap.add_argument("--packed", action="store_true")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     torch.manual_seed(0)
     for b in (int(v) for v in args.batches.split(",")):
         if args.step:
             step(b, args.ckpt)
         else:
-            kernels(b, args.iters)
+            kernels(b, args.iters, args.packed, args.repeats, args.seed)
 
 
 if __name__ == "__main__":

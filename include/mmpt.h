@@ -301,10 +301,25 @@ int mmpt_attention_varlen_bwd(int64_t batch, int64_t max_seq, int64_t total_toke
  * is the target for logits row r).  Writes per-row loss (0 for ignored rows) and,
  * if dlogits != NULL, dlogits = (softmax - onehot) * grad_scale in bf16
  * (dlogits may alias logits: fused fwd+bwd, one read of the logits).
+ * mmpt_cross_entropy_smooth adds TrainingArguments.label_smoothing_factor (HF Trainer's
+ * LabelSmoother) in the same pass.
  * ---------------------------------------------------------------------- */
 int mmpt_cross_entropy(int64_t rows, int64_t vocab, int64_t vocab_valid, const void* logits,
                        int64_t ld, const int64_t* labels, int64_t ignore_index, float grad_scale,
                        float* loss_rows, void* dlogits, int64_t ld_d, void* stream);
+/* The same with label smoothing (F.cross_entropy(label_smoothing = eps); HF's LabelSmoother,
+ * tf:trainer_pt_utils.py, which Trainer applies when label_smoothing_factor != 0).  With
+ * V = vocab_valid, a scored row has
+ *   loss = (1 - eps) (lse - x_y) + eps (lse - sum_{v<V} x_v / V),
+ *   dlogits_v = grad_scale (softmax_v - (1 - eps) [v = y] - eps / V) for v < V, 0 past V;
+ * an ignored row has loss 0 and gradient 0, a label outside [0, V) that is not ignore_index a
+ * NaN loss row and a zero gradient (as in mmpt_cross_entropy).  sum x comes from the pass that computes the
+ * softmax statistics: the same reads and writes as mmpt_cross_entropy.  label_smoothing must
+ * be finite and in [0, 1) (else MMPT_ERR_ARG); exactly 0 runs mmpt_cross_entropy's kernels. */
+int mmpt_cross_entropy_smooth(int64_t rows, int64_t vocab, int64_t vocab_valid, const void* logits,
+                              int64_t ld, const int64_t* labels, int64_t ignore_index,
+                              float grad_scale, float label_smoothing, float* loss_rows,
+                              void* dlogits, int64_t ld_d, void* stream);
 /* out[0] = Σ x[i] (deterministic).  workspace ≥ mmpt_sum_workspace_bytes(n). */
 int64_t mmpt_sum_workspace_bytes(int64_t n);
 int mmpt_sum_f32(int64_t n, const float* x, float* out, void* workspace, void* stream);

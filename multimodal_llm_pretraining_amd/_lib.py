@@ -64,6 +64,7 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_attention_varlen_bwd_workspace_bytes": (I64, [I64, I64, I64, I64]),
     "mmpt_attention_varlen_bwd": (I32, [I64, I64, I64, I64, I64, I64, P, I64, I64, I64, I64, I32, F32, P, P, P, I64, P, P, P, P]),
     "mmpt_cross_entropy": (I32, [I64, I64, I64, P, I64, P, I64, F32, P, P, I64, P]),
+    "mmpt_cross_entropy_smooth": (I32, [I64, I64, I64, P, I64, P, I64, F32, F32, P, P, I64, P]),
     "mmpt_sum_workspace_bytes": (I64, [I64]),
     "mmpt_sum_f32": (I32, [I64, P, P, P, P]),
     "mmpt_gather_rows_bf16": (I32, [I64, I64, P, P, I64, P, I64, P]),

@@ -26,7 +26,7 @@ from . import config as C
 from .distributed import sharding_to_mode
 from .optim import AdamConfig, min_lr_rate_of
 from .trainer import ManualTrainer as _StepTrainer
-from .trainer import StepConfig
+from .trainer import StepConfig, label_smoothing_from_args
 
 logger = logging.getLogger("academic-pretraining")
 
@@ -82,7 +82,11 @@ class ManualTrainer:
                               offload=tc.offload(),
                               scheduler=getattr(tc.scheduler_type, "value", tc.scheduler_type),
                               num_warmup_steps=warm, num_training_steps=tc.num_training_steps,
-                              min_lr_rate=min_lr_rate_of(sched_kw, adam.lr))
+                              min_lr_rate=min_lr_rate_of(sched_kw, adam.lr),
+                              # HF Trainer wraps the loss in LabelSmoother when the factor is
+                              # non-zero; here the cross-entropy kernels smooth
+                              label_smoothing=label_smoothing_from_args(
+                                  tc.hf_training_args_overrides, hf_args_overrides))
         if sharding_to_mode(sharding) in ("zero2", "zero3") and model.mmpt_config.classifier:
             raise NotImplementedError(  # before partition_out releases the module's storage
                 f"sharding {sharding!r} for the vision-only classifier "

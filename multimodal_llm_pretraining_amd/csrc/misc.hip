@@ -188,14 +188,64 @@ __device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
   return r;
 }
 
+// Label smoothing (SM = true; F.cross_entropy(label_smoothing = eps), HF's LabelSmoother): the
+// target is (1 - eps) on the label plus eps / V on each of the V = vocab_valid real classes,
+//   loss = (1 - eps) (lse - x_y) + eps (lse - sum_{v<V} x_v / V),
+//   dlogits_v = scale (softmax_v - (1 - eps) [v = y] - eps / V).
+// Both kernels below take sum x from the pass that computes the online max / sum (reduced over
+// the block together with the sum of exponentials: no further read, no further barrier) and
+// share these helpers, which fix every rounding (contraction off, the gradient one explicit
+// fma), so the register and the streaming form stay bitwise equal.
+__device__ __forceinline__ float ce_smooth_loss(float lse, float xlab, float sx, float eps,
+                                                int vocab_valid) {
+#pragma clang fp contract(off)
+  const float nll = lse - xlab;
+  const float uni = lse - sx / (float)vocab_valid;
+  const float a = (1.0f - eps) * nll;
+  const float b = eps * uni;
+  return a + b;
+}
+// One fma per element: e = exp(x - max), k = grad_scale / sum and the addend
+// kb = -grad_scale eps / V.  The label's element takes the addend kl = kb - grad_scale (1 - eps)
+// instead: its owner thread rewrites that one element of the chunk `o` it is about to store
+// (v: the chunk's logits), so no element pays a label compare.
+__device__ __forceinline__ void ce_smooth_label(v8s& o, const v8s v, int el, float gm, float k,
+                                                float kl) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    if (e == el) o[e] = (short)f2bf(__builtin_fmaf(__expf(bf2f((bf16_t)v[e]) - gm), k, kl));
+}
+
+// Two block sums behind one pair of barriers (each the bits of block_reduce(., sh, false)): the
+// smoothed kernels reduce sum x with the sum of exponentials instead of in a pass of its own.
+__device__ __forceinline__ float2 block_sum2(float a, float b, float* sh) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  __syncthreads();
+  if (l == 0) {
+    sh[w] = a;
+    sh[4 + w] = b;
+  }
+  __syncthreads();
+  float ra = sh[0], rb = sh[4];
+  for (int k = 1; k < 4; ++k) {
+    ra += sh[k];
+    rb += sh[4 + k];
+  }
+  return make_float2(ra, rb);
+}
+
 // vocab_valid <= vocab: logit columns >= vocab_valid are padding (a vocabulary padded to a
 // multiple of 8 for 16-B rows, e.g. Llama-3's 128256 + <image> = 128257 -> 128264): they
-// take no part in the softmax and get a zero gradient.
+// take no part in the softmax and get a zero gradient.  eps, gkb, gkl: SM only (the gradient's
+// two addends, see ce_smooth_label).
+template <bool SM>
 __global__ __launch_bounds__(256) void ce_kernel(int vocab, int vocab_valid, const bf16_t* logits,
                                                  long ld, const int64_t* labels, int64_t ignore,
                                                  float scale, float* loss_rows, bf16_t* dl,
-                                                 long ldd) {
-  __shared__ float sh[4];
+                                                 long ldd, float eps, float gkb, float gkl) {
+  __shared__ float sh[SM ? 8 : 4];
   const int row = blockIdx.x;
   const bf16_t* x = logits + (long)row * ld;
   const int64_t lab = labels[row];
@@ -207,6 +257,7 @@ __global__ __launch_bounds__(256) void ce_kernel(int vocab, int vocab_valid, con
   // the label's logit before any thread writes dlogits (which may alias the logits)
   const float xlab = threadIdx.x == 0 && !ign ? bf2f(x[lab]) : 0.f;
   float m = -INFINITY, s = 0.f;
+  [[maybe_unused]] float sx = 0.f;  // (SM) sum of this thread's valid logits, in column order
   for (int c = threadIdx.x; c < nv; c += 256) {
     const v8s v = *(const v8s*)(x + c * 8);
     float f[8];
@@ -215,6 +266,8 @@ __global__ __launch_bounds__(256) void ce_kernel(int vocab, int vocab_valid, con
     for (int e = 0; e < 8; ++e) {
       f[e] = c * 8 + e < vocab_valid ? bf2f((bf16_t)v[e]) : -INFINITY;
       mx = fmaxf(mx, f[e]);
+      if constexpr (SM)
+        if (c * 8 + e < vocab_valid) sx += f[e];
     }
     const float nm = fmaxf(m, mx);
     float acc = s * __expf(m - nm);
@@ -225,12 +278,27 @@ __global__ __launch_bounds__(256) void ce_kernel(int vocab, int vocab_valid, con
   }
   // combine (m, s) across the block
   const float gm = block_reduce(m, sh, true);
-  const float gs = block_reduce(m == -INFINITY ? 0.f : s * __expf(m - gm), sh, false);
+  float gs;
+  [[maybe_unused]] float gx = 0.f;
+  if constexpr (SM) {
+    const float2 r = block_sum2(m == -INFINITY ? 0.f : s * __expf(m - gm), sx, sh);
+    gs = r.x;
+    gx = r.y;
+  } else {
+    gs = block_reduce(m == -INFINITY ? 0.f : s * __expf(m - gm), sh, false);
+  }
   const float lse = gm + logf(gs);
-  if (threadIdx.x == 0) loss_rows[row] = bad ? __int_as_float(0x7fc00000) : ign ? 0.f : lse - xlab;
+  if constexpr (SM) {
+    const float nll = ce_smooth_loss(lse, xlab, gx, eps, vocab_valid);
+    if (threadIdx.x == 0) loss_rows[row] = bad ? __int_as_float(0x7fc00000) : ign ? 0.f : nll;
+  } else {
+    if (threadIdx.x == 0)
+      loss_rows[row] = bad ? __int_as_float(0x7fc00000) : ign ? 0.f : lse - xlab;
+  }
   if (dl == nullptr) return;
   bf16_t* d = dl + (long)row * ldd;
   const float inv = 1.0f / gs;
+  [[maybe_unused]] const float gk = inv * scale;
   for (int c = threadIdx.x; c < nv; c += 256) {
     const v8s v = *(const v8s*)(x + c * 8);
     v8s o;
@@ -238,12 +306,19 @@ __global__ __launch_bounds__(256) void ce_kernel(int vocab, int vocab_valid, con
     for (int e = 0; e < 8; ++e) {
       float g = 0.f;
       if (!ign && c * 8 + e < vocab_valid) {
-        g = __expf(bf2f((bf16_t)v[e]) - gm) * inv;
-        if (c * 8 + e == lab) g -= 1.0f;
-        g *= scale;
+        const float ex = __expf(bf2f((bf16_t)v[e]) - gm);
+        if constexpr (SM) {
+          g = __builtin_fmaf(ex, gk, gkb);
+        } else {
+          g = ex * inv;
+          if (c * 8 + e == lab) g -= 1.0f;
+          g *= scale;
+        }
       }
       o[e] = (short)f2bf(g);
     }
+    if constexpr (SM)
+      if (!ign && c == (int)(lab >> 3)) ce_smooth_label(o, v, (int)(lab & 7), gm, gk, gkl);
     *(v8s*)(d + c * 8) = o;
   }
 }
@@ -253,12 +328,12 @@ __global__ __launch_bounds__(256) void ce_kernel(int vocab, int vocab_valid, con
 // the online max / sum and every output are bitwise ce_kernel's) and the gradient pass reads
 // them from registers instead of from memory a second time: the logits are read once, 13 GB
 // per step less traffic at Pythia's 50,304-column rows (NC = 25: 100 VGPRs of row).
-template <int NC>
+template <int NC, bool SM>
 __global__ __launch_bounds__(256) void ce_reg_kernel(int vocab, int vocab_valid, const bf16_t* logits,
                                                      long ld, const int64_t* labels, int64_t ignore,
                                                      float scale, float* loss_rows, bf16_t* dl,
-                                                     long ldd) {
-  __shared__ float sh[4];
+                                                     long ldd, float eps, float gkb, float gkl) {
+  __shared__ float sh[SM ? 8 : 4];
   const int row = blockIdx.x;
   const bf16_t* x = logits + (long)row * ld;
   const int64_t lab = labels[row];
@@ -272,6 +347,7 @@ __global__ __launch_bounds__(256) void ce_reg_kernel(int vocab, int vocab_valid,
     buf[k] = c < nv ? *(const v8s*)(x + c * 8) : v8s{0, 0, 0, 0, 0, 0, 0, 0};
   }
   float m = -INFINITY, s = 0.f;
+  [[maybe_unused]] float sx = 0.f;  // (as ce_kernel)
 #pragma unroll
   for (int k = 0; k < NC; ++k) {
     const int c = threadIdx.x + k * 256;
@@ -282,6 +358,8 @@ __global__ __launch_bounds__(256) void ce_reg_kernel(int vocab, int vocab_valid,
     for (int e = 0; e < 8; ++e) {
       f[e] = c * 8 + e < vocab_valid ? bf2f((bf16_t)buf[k][e]) : -INFINITY;
       mx = fmaxf(mx, f[e]);
+      if constexpr (SM)
+        if (c * 8 + e < vocab_valid) sx += f[e];
     }
     const float nm = fmaxf(m, mx);
     float acc = s * __expf(m - nm);
@@ -291,7 +369,15 @@ __global__ __launch_bounds__(256) void ce_reg_kernel(int vocab, int vocab_valid,
     m = nm;
   }
   const float gm = block_reduce(m, sh, true);
-  const float gs = block_reduce(m == -INFINITY ? 0.f : s * __expf(m - gm), sh, false);
+  float gs;
+  [[maybe_unused]] float gx = 0.f;
+  if constexpr (SM) {
+    const float2 r = block_sum2(m == -INFINITY ? 0.f : s * __expf(m - gm), sx, sh);
+    gs = r.x;
+    gx = r.y;
+  } else {
+    gs = block_reduce(m == -INFINITY ? 0.f : s * __expf(m - gm), sh, false);
+  }
   const float lse = gm + logf(gs);
   // the label's logit from the owner thread's registers (with dlogits written in place, a
   // memory read could see another thread's gradient already)
@@ -305,11 +391,13 @@ __global__ __launch_bounds__(256) void ce_reg_kernel(int vocab, int vocab_valid,
 #pragma unroll
       for (int e = 0; e < 8; ++e)
         if (k == kl && e == el) xl = bf2f((bf16_t)buf[k][e]);
-    loss_rows[row] = lse - xl;
+    if constexpr (SM) loss_rows[row] = ce_smooth_loss(lse, xl, gx, eps, vocab_valid);
+    else loss_rows[row] = lse - xl;
   }
   if (dl == nullptr) return;
   bf16_t* d = dl + (long)row * ldd;
   const float inv = 1.0f / gs;
+  [[maybe_unused]] const float gk = inv * scale;
 #pragma unroll
   for (int k = 0; k < NC; ++k) {
     const int c = threadIdx.x + k * 256;
@@ -319,12 +407,19 @@ __global__ __launch_bounds__(256) void ce_reg_kernel(int vocab, int vocab_valid,
     for (int e = 0; e < 8; ++e) {
       float g = 0.f;
       if (!ign && c * 8 + e < vocab_valid) {
-        g = __expf(bf2f((bf16_t)buf[k][e]) - gm) * inv;
-        if (c * 8 + e == lab) g -= 1.0f;
-        g *= scale;
+        const float ex = __expf(bf2f((bf16_t)buf[k][e]) - gm);
+        if constexpr (SM) {
+          g = __builtin_fmaf(ex, gk, gkb);
+        } else {
+          g = ex * inv;
+          if (c * 8 + e == lab) g -= 1.0f;
+          g *= scale;
+        }
       }
       o[e] = (short)f2bf(g);
     }
+    if constexpr (SM)
+      if (!ign && c == (int)(lab >> 3)) ce_smooth_label(o, buf[k], (int)(lab & 7), gm, gk, gkl);
     *(v8s*)(d + c * 8) = o;
   }
 }
@@ -967,24 +1062,27 @@ int* misc_switch(const char* name, int* prev) {
 }
 }  // namespace mmpt
 
-extern "C" int mmpt_cross_entropy(int64_t rows, int64_t vocab, int64_t vocab_valid,
-                                  const void* logits, int64_t ld, const int64_t* labels,
-                                  int64_t ignore_index, float grad_scale, float* loss_rows,
-                                  void* dlogits, int64_t ld_d, void* stream) {
+template <bool SM>
+static int ce_launch(int64_t rows, int64_t vocab, int64_t vocab_valid, const void* logits,
+                     int64_t ld, const int64_t* labels, int64_t ignore_index, float grad_scale,
+                     float eps, float* loss_rows, void* dlogits, int64_t ld_d, void* stream) {
   MMPT_REQUIRE(rows > 0 && vocab > 0 && vocab % 8 == 0 && ld % 8 == 0 && ld_d % 8 == 0,
                "cross_entropy: vocab/ld must be multiples of 8");
   MMPT_REQUIRE(vocab_valid > 0 && vocab_valid <= vocab, "cross_entropy: bad vocab_valid");
   MMPT_REQUIRE(logits && labels && loss_rows, "cross_entropy: null pointer");
+  // the smoothed gradient's two addends (ce_smooth_label), rounded here once for both kernels
+  const float gkb = -(eps / (float)vocab_valid * grad_scale);
+  const float gkl = gkb - (1.0f - eps) * grad_scale;
   const int64_t nc = (vocab / 8 + 255) / 256;  // chunks of 8 logits per thread
   // the row in registers (one read of the logits) up to 32 chunks per thread (vocab <= 65,536;
   // a Llama-sized row would take 250 VGPRs: the two-pass kernel)
   if (nc > 0 && nc <= 32 && ce_reg()) {
     const unsigned g = (unsigned)rows;
     hipStream_t st = (hipStream_t)stream;
-#define MMPT_CE(NCV)                                                                           \
-  ce_reg_kernel<NCV><<<g, 256, 0, st>>>((int)vocab, (int)vocab_valid, (const bf16_t*)logits, ld, \
-                                        labels, ignore_index, grad_scale, loss_rows,           \
-                                        (bf16_t*)dlogits, ld_d)
+#define MMPT_CE(NCV)                                                                          \
+  ce_reg_kernel<NCV, SM><<<g, 256, 0, st>>>((int)vocab, (int)vocab_valid, (const bf16_t*)logits, \
+                                            ld, labels, ignore_index, grad_scale, loss_rows,  \
+                                            (bf16_t*)dlogits, ld_d, eps, gkb, gkl)
     if (nc <= 8) MMPT_CE(8);
     else if (nc <= 16) MMPT_CE(16);
     else if (nc <= 25) MMPT_CE(25);
@@ -992,10 +1090,33 @@ extern "C" int mmpt_cross_entropy(int64_t rows, int64_t vocab, int64_t vocab_val
 #undef MMPT_CE
     return check_launch("cross_entropy");
   }
-  ce_kernel<<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(
+  ce_kernel<SM><<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>(
       (int)vocab, (int)vocab_valid, (const bf16_t*)logits, ld, labels, ignore_index, grad_scale, loss_rows,
-      (bf16_t*)dlogits, ld_d);
+      (bf16_t*)dlogits, ld_d, eps, gkb, gkl);
   return check_launch("cross_entropy");
+}
+
+extern "C" int mmpt_cross_entropy(int64_t rows, int64_t vocab, int64_t vocab_valid,
+                                  const void* logits, int64_t ld, const int64_t* labels,
+                                  int64_t ignore_index, float grad_scale, float* loss_rows,
+                                  void* dlogits, int64_t ld_d, void* stream) {
+  return ce_launch<false>(rows, vocab, vocab_valid, logits, ld, labels, ignore_index, grad_scale,
+                          0.f, loss_rows, dlogits, ld_d, stream);
+}
+
+extern "C" int mmpt_cross_entropy_smooth(int64_t rows, int64_t vocab, int64_t vocab_valid,
+                                         const void* logits, int64_t ld, const int64_t* labels,
+                                         int64_t ignore_index, float grad_scale,
+                                         float label_smoothing, float* loss_rows, void* dlogits,
+                                         int64_t ld_d, void* stream) {
+  // (a NaN fails both comparisons)
+  MMPT_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f,
+               "cross_entropy_smooth: label_smoothing must be in [0, 1)");
+  if (label_smoothing == 0.f)  // the unsmoothed kernels, bit for bit mmpt_cross_entropy
+    return ce_launch<false>(rows, vocab, vocab_valid, logits, ld, labels, ignore_index,
+                            grad_scale, 0.f, loss_rows, dlogits, ld_d, stream);
+  return ce_launch<true>(rows, vocab, vocab_valid, logits, ld, labels, ignore_index, grad_scale,
+                         label_smoothing, loss_rows, dlogits, ld_d, stream);
 }
 
 extern "C" int64_t mmpt_sum_workspace_bytes(int64_t n) {

@@ -524,6 +524,9 @@ class Engine:
         # stream in the forward and recompute the layer's forward right before its
         # backward (the recompute is not counted as model FLOPs, as in the reference)
         self.checkpointing = False
+        # label smoothing of the loss (TrainingArguments.label_smoothing_factor, HF's
+        # LabelSmoother): every cross entropy below, training and forward-only, takes it
+        self.label_smoothing = 0.0
         # ZeRO-3 parameter residency (zero3.Zero3Residency): gathers a unit's weights
         # before use and reduce-scatters its gradients after its backward
         self.units = None
@@ -1230,7 +1233,8 @@ class Engine:
         logits = self._linear(y, "cls_head")
         loss_rows = self._e(B, dtype=F32)
         K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=cfg.num_classes)
+                        logits if need_grad else None, vocab_valid=cfg.num_classes,
+                        label_smoothing=self.label_smoothing)
         loss = self._e(1, dtype=F32)
         K.sum_f32(loss_rows, loss)
         if need_grad:
@@ -1404,7 +1408,8 @@ class Engine:
         logits = self._linear(y, "cls_head")
         loss_rows = self._e(B, dtype=F32)
         K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=cfg.num_classes)
+                        logits if need_grad else None, vocab_valid=cfg.num_classes,
+                        label_smoothing=self.label_smoothing)
         loss = self._e(1, dtype=F32)
         K.sum_f32(loss_rows, loss)
         if need_grad:
@@ -1587,7 +1592,8 @@ class Engine:
         K.gemm(n16, self.s.w("text.embed"), logits, bias=self.s.w("text.mlm.bias"))
         loss_rows = self._e(R, dtype=F32)
         K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=t.n_vocab)
+                        logits if need_grad else None, vocab_valid=t.n_vocab,
+                        label_smoothing=self.label_smoothing)
         loss = self._e(1, dtype=F32)
         K.sum_f32(loss_rows, loss)
         if need_grad:
@@ -1757,7 +1763,8 @@ class Engine:
         K.gemm(yf, self.s.w("text.embed"), logits)
         loss_rows = self._e(yf.shape[0], dtype=F32)
         K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=t.n_vocab)
+                        logits if need_grad else None, vocab_valid=t.n_vocab,
+                        label_smoothing=self.label_smoothing)
         loss = self._e(1, dtype=F32)
         K.sum_f32(loss_rows, loss)
         if need_grad:
@@ -1848,7 +1855,8 @@ class Engine:
         K.gemm(yf, self.s.w(self.head), logits)
         loss_rows = self._e(yf.shape[0], dtype=F32)
         K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=t.n_vocab)
+                        logits if need_grad else None, vocab_valid=t.n_vocab,
+                        label_smoothing=self.label_smoothing)
         loss = self._e(1, dtype=F32)
         K.sum_f32(loss_rows, loss)
         if need_grad:

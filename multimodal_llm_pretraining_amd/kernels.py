@@ -494,12 +494,19 @@ def attention_drop_bwd(qkv, heads, kv_heads, head_dim, head_stride, k_offset, v_
 
 # ----------------------------------------------------------------------------- loss
 def cross_entropy(logits, labels, ignore_index: int, grad_scale: float, loss_rows,
-                  dlogits=None, vocab_valid: int | None = None) -> None:
-    """vocab_valid: logit columns past it are padding (excluded, zero gradient)."""
+                  dlogits=None, vocab_valid: int | None = None,
+                  label_smoothing: float = 0.0) -> None:
+    """vocab_valid: logit columns past it are padding (excluded, zero gradient).
+    label_smoothing: F.cross_entropy's (eps / vocab_valid on every real class); 0 runs
+    mmpt_cross_entropy itself."""
     rows, vocab = logits.shape
-    _lib.call("mmpt_cross_entropy", rows, vocab, vocab_valid or vocab, logits.data_ptr(), _ld(logits),
-              labels.data_ptr(), ignore_index, float(grad_scale), loss_rows.data_ptr(),
-              _p(dlogits), 0 if dlogits is None else _ld(dlogits), _stream())
+    head = (rows, vocab, vocab_valid or vocab, logits.data_ptr(), _ld(logits), labels.data_ptr(),
+            ignore_index, float(grad_scale))
+    tail = (loss_rows.data_ptr(), _p(dlogits), 0 if dlogits is None else _ld(dlogits), _stream())
+    if label_smoothing == 0.0:
+        _lib.call("mmpt_cross_entropy", *head, *tail)
+    else:
+        _lib.call("mmpt_cross_entropy_smooth", *head, float(label_smoothing), *tail)
 
 
 def sum_f32(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:

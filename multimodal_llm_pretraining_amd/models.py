@@ -592,10 +592,16 @@ class MMPTForPretraining(nn.Module):
                       attention_mask=attention_mask, position_ids=position_ids)
         denom = float(num_items_in_batch) if num_items_in_batch is not None \
             else float(max(1, batch.num_items))
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._plist):
-            loss = _EngineStep.apply(self, batch, denom, *self._plist)
-        else:  # evaluation: no dlogits, no activation cache
-            loss = (self.engine.forward(batch, 1.0 / denom, need_grad=False) / denom).view(())
+        # the model's own loss is unsmoothed (HF applies label_smoothing_factor in the Trainer,
+        # not in the model), also while a trainer that smooths shares this engine
+        eps, self.engine.label_smoothing = self.engine.label_smoothing, 0.0
+        try:
+            if torch.is_grad_enabled() and any(p.requires_grad for p in self._plist):
+                loss = _EngineStep.apply(self, batch, denom, *self._plist)
+            else:  # evaluation: no dlogits, no activation cache
+                loss = (self.engine.forward(batch, 1.0 / denom, need_grad=False) / denom).view(())
+        finally:
+            self.engine.label_smoothing = eps
         return MMPTOutput(loss=loss)
 
 

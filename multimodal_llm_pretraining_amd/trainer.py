@@ -42,6 +42,30 @@ class StepConfig:
     num_warmup_steps: int = 0
     num_training_steps: int = 1
     min_lr_rate: float = 0.0
+    # TrainingArguments.label_smoothing_factor: the loss is F.cross_entropy's with
+    # label_smoothing (HF Trainer's LabelSmoother), in training and in forward-only steps
+    label_smoothing: float = 0.0
+
+    def __post_init__(self):
+        self.label_smoothing = check_label_smoothing(self.label_smoothing)
+
+
+def check_label_smoothing(value, name: str = "label_smoothing") -> float:
+    """The factor as a float; ValueError unless it is finite and in [0, 1)."""
+    eps = float(value)
+    if not 0.0 <= eps < 1.0:  # (NaN fails both comparisons)
+        raise ValueError(f"{name} must be in [0, 1), got {value!r}")
+    return eps
+
+
+def label_smoothing_from_args(*args: dict) -> float:
+    """`label_smoothing_factor` of TrainingArguments dicts merged left to right (a later dict
+    wins, as a per-call override wins over the model class's for weight_decay); absent = 0."""
+    merged: dict = {}
+    for a in args:
+        merged.update(a or {})
+    return check_label_smoothing(merged.get("label_smoothing_factor", 0.0),
+                                 "label_smoothing_factor")
 
 
 class ManualTrainer:
@@ -114,6 +138,7 @@ class ManualTrainer:
         self.store = store
         self.engine = engine if engine is not None else Engine(self.cfg, self.store)
         self.engine.checkpointing = step_cfg.activation_checkpointing
+        self.engine.label_smoothing = step_cfg.label_smoothing
         if self.unit_mode:
             self.sync = Zero3Sync(self.store, self.engine.unit_order(), group,
                                   quant=step_cfg.sharding == "zero_3++")

@@ -11,7 +11,9 @@ MI355X step instead of a transformers.Trainer over DeepSpeed/FSDP.
 TrainingArguments keys honoured (everything the reference's JSON sets):
   per_device_train_batch_size, gradient_accumulation_steps, max_steps, lr_scheduler_type,
   lr_scheduler_kwargs.min_lr_rate, warmup_steps, gradient_checkpointing, bf16 (must be
-  true: the step computes in bf16 autocast semantics), max_grad_norm, seed, and the
+  true: the step computes in bf16 autocast semantics), max_grad_norm, seed,
+  label_smoothing_factor (default 0; HF Trainer's LabelSmoother: the cross-entropy kernels
+  smooth on the GPU, LabelSmoother itself on the CPU path), and the
   sharding given by `deepspeed.zero_optimization` (stage, offload_optimizer,
   offload_param) or `fsdp` ("shard_grad_op" / "full_shard" / "hybrid_shard[_zero2]"
   + "offload").  tf32 / torch_compile / fsdp_config are accepted and have no effect.
@@ -97,6 +99,20 @@ def _log(output_dir: str, rec: dict) -> None:
         f.write(json.dumps(rec) + "\n")
 
 
+def smoothed_loss(model, model_config, batch: dict, factor: float, num_items: int):
+    """Trainer.compute_loss with label_smoothing_factor: the model runs without labels and HF's
+    LabelSmoother scores its logits over `num_items`.  Labels are shifted for every causal
+    model — by the model's kind, not by its class name as Trainer decides it (which would
+    leave LlavaForConditionalGeneration unshifted)."""
+    from transformers.trainer_pt_utils import LabelSmoother
+
+    text = model_config.text
+    shift = not model_config.classifier and not text.roberta
+    inputs = {k: v for k, v in batch.items() if k != "labels"}
+    return LabelSmoother(epsilon=factor)(model(**inputs), batch["labels"], shift_labels=shift,
+                                         num_items_in_batch=num_items)
+
+
 def train_cpu(output_dir: str, model_type: str, training_arguments: dict,
               max_steps: int | None = None, log_every: int = 1) -> list[dict]:
     """BASELINE C1: the naive eager model on the CPU, world size 1, fp32."""
@@ -104,8 +120,10 @@ def train_cpu(output_dir: str, model_type: str, training_arguments: dict,
 
     from multimodal_llm_pretraining_amd.models import get_model_class
     from multimodal_llm_pretraining_amd.optim import Schedule, min_lr_rate_of
+    from multimodal_llm_pretraining_amd.trainer import label_smoothing_from_args
 
     a = training_arguments
+    smoothing = label_smoothing_from_args(a)
     if int(os.environ.get("WORLD_SIZE", "1")) != 1:
         raise NotImplementedError("the CPU path runs at world size 1 (BASELINE C1)")
     mc = get_model_class(model_type)
@@ -143,7 +161,10 @@ def train_cpu(output_dir: str, model_type: str, training_arguments: dict,
             gr["lr"] = lr
         total = 0.0
         for b in micro:
-            loss = model(**b, num_items_in_batch=n_items).loss
+            if smoothing:  # Trainer.compute_loss with a label_smoother
+                loss = smoothed_loss(model, mc.model_config, b, smoothing, n_items)
+            else:
+                loss = model(**b, num_items_in_batch=n_items).loss
             loss.backward()
             total += loss.item()
         if clip > 0:
@@ -170,7 +191,8 @@ def train(output_dir: str, model_type: str, training_arguments: dict, max_steps:
 
     from multimodal_llm_pretraining_amd.models import get_model_class
     from multimodal_llm_pretraining_amd.optim import min_lr_rate_of
-    from multimodal_llm_pretraining_amd.trainer import ManualTrainer, StepConfig
+    from multimodal_llm_pretraining_amd.trainer import (ManualTrainer, StepConfig,
+                                                        label_smoothing_from_args)
 
     a = training_arguments
     if not a.get("bf16", False) or a.get("fp16", False):
@@ -196,7 +218,8 @@ def train(output_dir: str, model_type: str, training_arguments: dict, max_steps:
                    scheduler=str(a.get("lr_scheduler_type", "linear")),
                    num_warmup_steps=int(a.get("warmup_steps", 0)),
                    num_training_steps=int(a.get("max_steps", steps)),
-                   min_lr_rate=min_lr_rate_of(sched_kw, adam.lr)),
+                   min_lr_rate=min_lr_rate_of(sched_kw, adam.lr),
+                   label_smoothing=label_smoothing_from_args(a)),
         adam, device, model_cfg=mc.model_config)
     ds = mc.load_dummy_dataset()
     os.makedirs(output_dir, exist_ok=True)

@@ -1,0 +1,211 @@
+"""CPU-only tests of label smoothing (include/mmpt.h K12, mmpt_cross_entropy_smooth).
+
+* The fp64 row formulas of tests/label_smoothing_ref.py are F.cross_entropy(label_smoothing=eps)
+  and its autograd gradient to 1e-12 (ignored rows included), and HF's LabelSmoother — shifted
+  [B, S, V] labels and [B, V] / [B] classification labels — to 1e-6 relative (LabelSmoother sums
+  its log-probabilities in fp32: the looser side; measured 2e-8).
+* include/mmpt.h and _lib.py agree on the new signature, MMPT_ABI_VERSION is still 16 and the
+  library exports the symbol.
+* The TrainingArguments helper: absent = 0, validation, a later dict wins; StepConfig validates.
+* scripts/training.py's CPU path: LabelSmoother over the plain transformers model's logits.
+"""
+
+import math
+import os
+import re
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import label_smoothing_ref as LS  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ------------------------------------------------------------------ reference formulas
+@pytest.mark.parametrize("eps", [0.0, 0.1, 0.9])
+def test_rows_are_torch_cross_entropy(eps):
+    g = torch.Generator().manual_seed(0)
+    R, V = 23, 61
+    x = (torch.randn(R, V, generator=g, dtype=torch.float64) * 3).requires_grad_()
+    labels = torch.randint(0, V, (R,), generator=g)
+    labels[::5] = -100
+    labels[1], labels[2] = 0, V - 1
+    w = torch.randn(R, generator=g, dtype=torch.float64)  # a cotangent per row
+    ref = F.cross_entropy(x, labels, ignore_index=-100, label_smoothing=eps, reduction="none")
+    (ref * w).sum().backward()
+    loss, d, _ = LS.ce_rows(x.detach(), labels, eps)
+    assert (loss - ref.detach()).abs().max().item() < 1e-12
+    assert (d * w[:, None] - x.grad).abs().max().item() < 1e-12
+    assert loss[::5].eq(0).all() and d[::5].eq(0).all()
+    # grad_scale scales the gradient only
+    _, d2, _ = LS.ce_rows(x.detach(), labels, eps, grad_scale=0.25)
+    assert torch.equal(d2, 0.25 * d)
+
+
+def test_rows_padded_vocabulary_and_bad_label():
+    g = torch.Generator().manual_seed(1)
+    R, V, vv = 9, 64, 59
+    x = torch.randn(R, V, generator=g, dtype=torch.float64) * 3
+    labels = torch.randint(0, vv, (R,), generator=g)
+    labels[3] = -100
+    ref = F.cross_entropy(x[:, :vv], labels, ignore_index=-100, label_smoothing=0.1,
+                          reduction="none")
+    loss, d, p = LS.ce_rows(x, labels, 0.1, vocab_valid=vv)
+    assert (loss - ref).abs().max().item() < 1e-12
+    assert d[:, vv:].eq(0).all() and p[:, vv:].eq(0).all()
+    labels[5] = vv  # a padding column is no class
+    loss2, d2, _ = LS.ce_rows(x, labels, 0.1, vocab_valid=vv)
+    assert math.isnan(loss2[5].item()) and d2[5].eq(0).all()
+    keep = torch.arange(R) != 5
+    assert torch.equal(loss2[keep], loss[keep]) and torch.equal(d2[keep], d[keep])
+
+
+@pytest.mark.parametrize("eps", [0.1, 0.9])
+def test_rows_are_hf_label_smoother(eps):
+    from transformers.trainer_pt_utils import LabelSmoother
+
+    g = torch.Generator().manual_seed(2)
+    smoother = LabelSmoother(epsilon=eps)
+    # causal: [B, S, V] logits, labels shifted by the smoother
+    B, S, V = 3, 11, 47
+    x = (torch.randn(B, S, V, generator=g, dtype=torch.float64) * 3).requires_grad_()
+    labels = torch.randint(0, V, (B, S), generator=g)
+    labels[:, :4] = -100
+    labels[1, 7] = -100
+    hf = smoother({"logits": x}, labels, shift_labels=True)
+    hf.backward()
+    rows, lab = x.detach()[:, :-1].reshape(-1, V), labels[:, 1:].reshape(-1)
+    n = int((lab != -100).sum())
+    loss, d, _ = LS.ce_rows(rows, lab, eps, grad_scale=1.0 / n)
+    assert abs(loss.sum().item() / n - hf.item()) < 1e-6 * abs(hf.item())
+    got = x.grad[:, :-1].reshape(-1, V)
+    assert (d - got).norm().item() < 1e-6 * got.norm().item()
+    assert x.grad[:, -1].eq(0).all()
+    # classification: [B, V] logits, [B] labels, no shift
+    B, V = 13, 10
+    x = (torch.randn(B, V, generator=g, dtype=torch.float64) * 3).requires_grad_()
+    labels = torch.randint(0, V, (B,), generator=g)
+    hf = smoother({"logits": x}, labels)
+    hf.backward()
+    loss, d, _ = LS.ce_rows(x.detach(), labels, eps, grad_scale=1.0 / B)
+    assert abs(loss.sum().item() / B - hf.item()) < 1e-6 * abs(hf.item())
+    assert (d - x.grad).norm().item() < 1e-6 * x.grad.norm().item()
+
+
+def test_patch_smooths_f_cross_entropy_and_restores():
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(5, 7, generator=g)
+    y = torch.randint(0, 7, (5,), generator=g)
+    orig = F.cross_entropy
+    with LS.smoothed_cross_entropy(0.1):
+        inside = F.cross_entropy(x, y, reduction="sum")
+    assert F.cross_entropy is orig
+    assert torch.equal(inside, orig(x, y, reduction="sum", label_smoothing=0.1))
+    assert not torch.equal(inside, orig(x, y, reduction="sum"))
+
+
+# ------------------------------------------------------------------ header / binding
+def test_header_and_binding_agree():
+    from multimodal_llm_pretraining_amd import _lib
+
+    src = open(os.path.join(ROOT, "include", "mmpt.h")).read()
+    assert re.search(r"#define MMPT_ABI_VERSION (\d+)", src).group(1) == "16"  # entries only added
+    assert _lib.ABI_VERSION == 16
+    ctypes_of = {"int64_t": "I64", "int": "I32", "float": "F32"}
+    sigs = {}
+    for name in ("mmpt_cross_entropy", "mmpt_cross_entropy_smooth"):
+        m = re.search(r"\bint " + name + r"\s*\(([^)]*)\)\s*;", src)
+        assert m, name
+        args = [" ".join(a.split()) for a in m.group(1).split(",")]
+        types = ["P" if "*" in a else ctypes_of[a.rsplit(" ", 1)[0]] for a in args]
+        res, argtypes = _lib.SIGNATURES[name]
+        assert res is _lib.I32 and argtypes == [getattr(_lib, t) for t in types], (name, types)
+        sigs[name] = [a.rsplit(" ", 1)[1].lstrip("*") for a in args]
+    # the unsmoothed entry's arguments with label_smoothing after grad_scale
+    at = sigs["mmpt_cross_entropy"].index("grad_scale") + 1
+    want = sigs["mmpt_cross_entropy"][:at] + ["label_smoothing"] + sigs["mmpt_cross_entropy"][at:]
+    assert sigs["mmpt_cross_entropy_smooth"] == want
+    lib = _lib.load()
+    assert lib.mmpt_abi_version() == 16
+    assert hasattr(lib, "mmpt_cross_entropy_smooth")
+
+
+# ------------------------------------------------------------------ TrainingArguments helper
+def test_label_smoothing_from_args():
+    from multimodal_llm_pretraining_amd.trainer import label_smoothing_from_args as f
+
+    assert f({}) == 0.0 and f() == 0.0 and f({"weight_decay": 0.1}) == 0.0
+    assert f({"label_smoothing_factor": 0.1}) == 0.1
+    assert f({"label_smoothing_factor": 0}) == 0.0
+    for bad in (-0.1, 1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="label_smoothing_factor"):
+            f({"label_smoothing_factor": bad})
+    # a per-call override wins over the model class's, as for weight_decay
+    assert f({"label_smoothing_factor": 0.1}, {"label_smoothing_factor": 0.2}) == 0.2
+    assert f({"label_smoothing_factor": 0.1}, {}) == 0.1
+    assert f({"label_smoothing_factor": 0.1}, {"label_smoothing_factor": 0.0}) == 0.0
+
+
+def test_step_config_validates():
+    from multimodal_llm_pretraining_amd.trainer import StepConfig
+
+    assert StepConfig().label_smoothing == 0.0
+    assert StepConfig(label_smoothing=0.1).label_smoothing == 0.1
+    for bad in (-0.1, 1.0, float("nan")):
+        with pytest.raises(ValueError, match="label_smoothing"):
+            StepConfig(label_smoothing=bad)
+
+
+def test_engine_default_and_kernel_argument():
+    import inspect
+
+    from multimodal_llm_pretraining_amd import kernels
+    from multimodal_llm_pretraining_amd.engine import Engine
+
+    assert inspect.signature(kernels.cross_entropy).parameters["label_smoothing"].default == 0.0
+    src = inspect.getsource(Engine)
+    assert src.count("K.cross_entropy(") == src.count("label_smoothing=self.label_smoothing") == 5
+
+
+# ------------------------------------------------------------------ scripts/training.py, CPU path
+@pytest.mark.parametrize("name", ["tiny-lm", "tiny-roberta", "tiny-vit-cls"])
+def test_training_script_cpu_path_smooths(name):
+    """train_cpu's loss with label_smoothing_factor: HF's LabelSmoother over the plain transformers
+    model's logits, on the rows the model itself scores (shifted for the causal model, unshifted
+    for the MLM, one per image for the classifier), over num_items."""
+    import importlib.util
+
+    from multimodal_llm_pretraining_amd import config as C
+    from multimodal_llm_pretraining_amd.models import build_hf_model
+
+    spec = importlib.util.spec_from_file_location("training_script",
+                                                  os.path.join(ROOT, "scripts", "training.py"))
+    script = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(script)
+    cfg = C.get_config(name)
+    torch.manual_seed(0)
+    model = build_hf_model(cfg).eval()
+    g = torch.Generator().manual_seed(1)
+    if cfg.classifier:
+        labels = torch.randint(0, cfg.num_classes, (4,), generator=g)
+        batch = {"pixel_values": torch.rand(4, 3, cfg.vision.image, cfg.vision.image, generator=g),
+                 "labels": labels}
+    else:
+        ids = torch.randint(3, cfg.text.n_vocab, (2, 12), generator=g)
+        labels = ids.clone()
+        labels[:, :3] = -100
+        batch = {"input_ids": ids, "labels": labels}
+    with torch.no_grad():
+        logits = model(**{k: v for k, v in batch.items() if k != "labels"}).logits
+        if not cfg.classifier and not cfg.text.roberta:
+            logits, labels = logits[:, :-1], labels[:, 1:]
+        n = int((labels != -100).sum())
+        got = script.smoothed_loss(model, cfg, batch, 0.1, n).item()
+        plain = model(**batch).loss.item()
+    want, _, _ = LS.ce_rows(logits.reshape(-1, logits.shape[-1]), labels.reshape(-1), 0.1)
+    assert abs(got - want.sum().item() / n) < 1e-5
+    assert abs(got - plain) > 1e-3

@@ -714,6 +714,60 @@ int mmpt_unpatchify2_nhwc(int64_t B, int64_t H, int64_t W, int64_t C, const void
                           void* stream);
 
 /* ------------------------------------------------------------------------
+ * K21 stochastic depth (ConvNextDropPath, ConvNextConfig.drop_path_rate): in training, sample b of
+ * a block with drop probability p is either kept, out_b = x_b + (gamma * y_b) / keep_prob, or
+ * dropped, out_b = x_b.  A dropped sample's branch contributes nothing to the output or to any
+ * gradient, so the block runs over its Bk kept samples only: the bf16 side of every kernel is
+ * compact [Bk][...], the fp32 residual stream stays dense [B][...] and is addressed through
+ *   idx  int32 [Bk], device memory, strictly increasing, idx[b'] in [0, B): the plane of compact
+ *        sample b' in the stream;
+ *   slot int32 [B], device memory: the compact index of plane b, or -1 where it is dropped.
+ * The keep bits are K16's: sample b is element b of a dropout site, kept iff its Philox word >=
+ * floor(p * 2^32), so mmpt_dropout_mask(n = B, p, seed, site) describes them; the caller decides
+ * on the host (the rule is a pure function of p, seed, site) and passes idx / slot.
+ * Roundings, with s = float(1 / (1 - p)) (philox.h dropout_scale: one fp32 factor; a device
+ * division by a scalar is that multiplication):
+ *   forward   out = resid + s * (gamma * f32(y)): the product gamma * f32(y) rounded to fp32, that
+ *             times s rounded to fp32, the sum with the residual rounded to fp32;
+ *   backward  g' = g * s rounded to fp32, then mmpt_layerscale_bwd with g' for g:
+ *             dy = bf16(gamma * g'), dgamma += Σ g' * f32(y) over the kept samples' rows only.
+ * A map entry outside [0, B) (or a slot outside [0, Bk)) is never followed: that sample is left
+ * out (treated as dropped).  1 <= Bk <= B (mmpt_droppath_add_fwd: 0 <= Bk), C % 8 == 0 and
+ * C <= 4096, 16-B aligned pointers (the int32 tables: 4-B), 0 <= p < 1; else MMPT_ERR_ARG
+ * (nothing is launched).  Added without a change of MMPT_ABI_VERSION: the entries are new,
+ * nothing existing changed.
+ * ---------------------------------------------------------------------- */
+/* mmpt_dwconv7_fwd over the kept planes: c[b'] = conv(x[idx[b']]).  x fp32 [B][H][W][C],
+ * c bf16 [Bk][H][W][C]; there is no gather pass, the convolution reads x through the map. */
+int mmpt_dwconv7_idx_fwd(int64_t B, int64_t Bk, int64_t H, int64_t W, int64_t C, const float* x,
+                         const void* idx, const void* w, const void* bias, void* c, void* stream);
+/* mmpt_dwconv7_bwd_input over the kept planes: dx_out[idx[b']] = dx_in[idx[b']] + f32(bf16(convT(
+ * dc[b']))).  dc bf16 [Bk][H][W][C]; dx_in (NULL: zero; may alias dx_out) and dx_out fp32
+ * [B][H][W][C].  Planes that idx does not name are neither read nor written. */
+int mmpt_dwconv7_idx_bwd_input(int64_t B, int64_t Bk, int64_t H, int64_t W, int64_t C,
+                               const void* dc, const void* idx, const void* w, const float* dx_in,
+                               float* dx_out, void* stream);
+/* mmpt_dwconv7_bwd_weight over the kept planes: x fp32 [B][H][W][C] read at idx[b'], dc bf16
+ * [Bk][H][W][C].  Workspace: mmpt_dwconv7_bwd_weight_workspace_bytes(Bk, H, W, C). */
+int mmpt_dwconv7_idx_bwd_weight(int64_t B, int64_t Bk, int64_t H, int64_t W, int64_t C,
+                                const float* x, const void* idx, const void* dc, float* dw,
+                                float* db, void* workspace, void* stream);
+/* The block's residual in one pass over the dense stream: plane b with slot[b] >= 0 gets the
+ * forward rule above from y's compact plane slot[b], every other plane is copied.  resid, out fp32
+ * dense [B][rows_per_sample][C] (out may alias resid); y bf16 [Bk*rows_per_sample][ld_y] (NULL
+ * allowed when Bk == 0); gamma fp32 [C]. */
+int mmpt_droppath_add_fwd(int64_t B, int64_t Bk, int64_t rows_per_sample, int64_t C,
+                          const float* resid, const float* gamma, const void* y, int64_t ld_y,
+                          const void* slot, double p, float* out, void* stream);
+int64_t mmpt_droppath_bwd_workspace_bytes(int64_t Bk, int64_t rows_per_sample, int64_t C);
+/* The backward rule above: g fp32 dense [B][rows_per_sample][C] read at the planes idx names;
+ * y bf16 [Bk*rows_per_sample][ld_y], dy bf16 [Bk*rows_per_sample][ld_dy] compact; dgamma fp32 [C]
+ * += through mmpt_layerscale_bwd's two-stage reduction in fixed order (no atomics). */
+int mmpt_droppath_bwd(int64_t B, int64_t Bk, int64_t rows_per_sample, int64_t C, const float* g,
+                      const void* idx, const float* gamma, const void* y, int64_t ld_y, double p,
+                      void* dy, int64_t ld_dy, float* dgamma, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------
  * K22  Mamba (tf:models/mamba/modeling_mamba.py MambaMixer): the causal depthwise conv1d and the
  * selective scan, the two ops the reference takes from causal-conv1d and mamba-ssm.  Rows are
  * tokens (b, t), T = B*L rows in all; channels are contiguous and every activation has an explicit

@@ -120,6 +120,12 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_dwconv7_bwd_input": (I32, [I64, I64, I64, I64, P, P, P, P, P]),
     "mmpt_dwconv7_bwd_weight_workspace_bytes": (I64, [I64, I64, I64, I64]),
     "mmpt_dwconv7_bwd_weight": (I32, [I64, I64, I64, I64, P, P, P, P, P, P]),
+    "mmpt_dwconv7_idx_fwd": (I32, [I64, I64, I64, I64, I64, P, P, P, P, P, P]),
+    "mmpt_dwconv7_idx_bwd_input": (I32, [I64, I64, I64, I64, I64, P, P, P, P, P, P]),
+    "mmpt_dwconv7_idx_bwd_weight": (I32, [I64, I64, I64, I64, I64, P, P, P, P, P, P, P]),
+    "mmpt_droppath_add_fwd": (I32, [I64, I64, I64, I64, P, P, P, I64, P, F64, P, P]),
+    "mmpt_droppath_bwd_workspace_bytes": (I64, [I64, I64, I64]),
+    "mmpt_droppath_bwd": (I32, [I64, I64, I64, I64, P, P, P, P, I64, F64, P, I64, P, P, P]),
     "mmpt_layerscale_add_fwd": (I32, [I64, I64, P, P, P, I64, P, P]),
     "mmpt_layerscale_bwd_workspace_bytes": (I64, [I64, I64]),
     "mmpt_layerscale_bwd": (I32, [I64, I64, P, P, P, I64, P, I64, P, P, P]),

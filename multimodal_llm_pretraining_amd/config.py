@@ -208,7 +208,8 @@ class ConvNextConfig:
     ConvNextLayer blocks (7x7 depthwise conv, LayerNorm, 4x pointwise MLP with erf-GELU, layer
     scale gamma, residual) with a LayerNorm + 2x2/s2 conv downsample in front of stages 1-3,
     then the global average pool, a LayerNorm (head_eps = ConvNextConfig.layer_norm_eps) and the
-    classifier.  drop_path_rate is 0 in every configuration the reference builds."""
+    classifier.  drop_path_rate (ConvNextConfig.drop_path_rate: stochastic depth, per-block rates
+    rising linearly from 0) is 0 in every configuration the reference builds."""
 
     hidden_sizes: tuple = (96, 192, 384, 768)
     depths: tuple = (3, 3, 9, 3)
@@ -218,8 +219,10 @@ class ConvNextConfig:
     eps: float = 1e-6
     head_eps: float = 1e-12
     layer_scale_init: float = 1e-6
+    drop_path_rate: float = 0.0
 
     def __post_init__(self):
+        _check_dropout(self.drop_path_rate, "ConvNextConfig", "drop_path_rate")
         if len(self.hidden_sizes) != 4 or len(self.depths) != 4:
             raise ValueError("ConvNextConfig: four stages (hidden_sizes and depths of length 4)")
         if any(c <= 0 or c % 8 for c in self.hidden_sizes) or any(d <= 0 for d in self.depths):
@@ -236,6 +239,13 @@ class ConvNextConfig:
     def side(self, stage: int) -> int:
         """H = W of a stage's plane."""
         return self.image // self.patch >> stage
+
+    def drop_path_rates(self) -> tuple:
+        """Drop probability of block j, counted over all stages, as HF's ConvNextEncoder has it:
+        torch.linspace(0, drop_path_rate, sum(depths)).tolist() — fp32 values held as Python
+        floats; block 0 is never dropped."""
+        import torch
+        return tuple(torch.linspace(0, self.drop_path_rate, sum(self.depths)).tolist())
 
 
 @dataclass(frozen=True)
@@ -450,6 +460,20 @@ def with_dropout(cfg: ModelConfig, text: float = 0.0, vision: float = 0.0, *,
                                   attention_dropout=vision_attention))
 
 
+def with_drop_path(cfg: ModelConfig, rate: float) -> ModelConfig:
+    """`cfg` with ConvNextConfig.drop_path_rate set.  Only ConvNeXt has stochastic depth among the
+    families here (HF's ViT, CLIP, GPTNeoX, Llama, RoBERTa and Mamba have no drop path): any
+    other model raises ValueError."""
+    if cfg.convnext is None:
+        raise ValueError("drop_path_rate on a model without a ConvNeXt backbone: HF has no drop "
+                         "path for this family")
+    return replace(cfg, convnext=replace(cfg.convnext, drop_path_rate=rate))
+
+
+# stochastic depth on the tiny ConvNeXt: block rates 0 .. 0.5, and 0 .. 0.8 (whole blocks with no
+# sample kept at B = 2)
+PRESETS["tiny-convnext-dp"] = with_drop_path(PRESETS["tiny-convnext"], 0.5)
+PRESETS["tiny-convnext-dp8"] = with_drop_path(PRESETS["tiny-convnext"], 0.8)
 # attention-probability dropout 0.1 (tiny-mm-adrop: hidden and attention dropout on both sides)
 PRESETS["tiny-lm-adrop"] = with_dropout(PRESETS["tiny-lm"], text_attention=0.1)
 PRESETS["tiny-mm-adrop"] = with_dropout(PRESETS["tiny-mm"], 0.1, 0.1, text_attention=0.1,
@@ -630,7 +654,9 @@ def _convnext_flops(cfg: ModelConfig, executed: bool = False) -> float:
     need none).  The counter's formula for a convolution's weight gradient multiplies the output
     channels by the batch-transposed input channels, so for the depthwise conv (groups = C) it
     reports C times the MACs executed: restated here as the counter has it.  `executed`: that
-    gradient at the 2·MACs it takes (the count behind `executed_mfu`)."""
+    gradient at the 2·MACs it takes (the count behind `executed_mfu`).  With drop_path_rate > 0
+    the whole block is still counted for every sample, as HF executes it (it computes the branch
+    and multiplies by zero); the engine skips the dropped samples' block work."""
     cn = cfg.convnext
     hw = cn.side(0) ** 2
     total = 2 * 2 * hw * cn.hidden_sizes[0] * cn.channels * cn.patch ** 2

@@ -14,9 +14,16 @@
 //
 // Reductions over rows (dw, db, dgamma, the pool) are per-workgroup partials summed in a fixed
 // order by a second kernel: no atomics, bitwise reproducible.
+//
+// Stochastic depth (ConvNextDropPath): a block runs over its kept samples only.  The depthwise
+// kernels take a template flag IDX: the fp32 stream (x, dx_in / dx_out) is then addressed through
+// idx[b'] (compact sample b' -> source plane) while the bf16 side stays compact [Bk][H][W][C]; the
+// dense instantiations (IDX = false) never read the map.  droppath_add / droppath_bwd are the
+// layer-scale residual and its backward over the kept samples with the factor 1 / keep_prob.
 #include <algorithm>
 
 #include "common.h"
+#include "philox.h"
 
 namespace mmpt {
 namespace {
@@ -38,6 +45,8 @@ struct DwArgs {
   float* o32;                  // bwd_input: dx_out
   float* partials;             // bwd_weight
   int nb;                      // bwd_weight: workgroups per channel chunk
+  const int* idx;              // IDX kernels: plane of compact sample b' in the fp32 stream
+  int planes;                  // IDX kernels: planes in the fp32 stream (idx[b'] < planes)
 };
 
 __device__ __forceinline__ void unpack8(const uint4 u, float* f) {
@@ -91,7 +100,7 @@ __device__ __forceinline__ void stage_tile(const DwArgs& a, const void* src, uin
 
 // forward (BWD = false): c = bf16(acc + bias); input gradient (BWD = true): the same correlation
 // over dc with the filter flipped, dx_out = dx_in + f32(bf16(acc)).
-template <bool BWD, int P>
+template <bool BWD, int P, bool IDX = false>
 __global__ __launch_bounds__(256) void dwconv7_kernel(const DwArgs a) {
   __shared__ uint4 sw[49 * 8];
   __shared__ uint4 st[P * P * 8];
@@ -99,13 +108,16 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const DwArgs a) {
   const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
   const int chunk = blockIdx.y;
   const int y0 = (tile / a.tiles_x) * a.TH, x0 = (tile % a.tiles_x) * a.TW;
+  // the plane of the fp32 side: through the map, and a map entry outside the stream does nothing
+  const int bs = IDX ? a.idx[b] : b;
+  if (IDX && (unsigned)bs >= (unsigned)a.planes) return;
   for (int i = threadIdx.x; i < 49 * 8; i += blockDim.x) {
     const int g = i & 7, tap = i >> 3, gg = chunk * 8 + g;
     const int ts = BWD ? 48 - tap : tap;
     sw[i] = gg < a.G ? *(const uint4*)(a.w + (long)ts * a.C + gg * 8) : make_uint4(0u, 0u, 0u, 0u);
   }
   if (BWD) stage_tile<false>(a, a.x16, st, b, chunk, y0 - 3, x0 - 3, a.PH, a.PW, a.PH, a.PW);
-  else stage_tile<true>(a, a.x32, st, b, chunk, y0 - 3, x0 - 3, a.PH, a.PW, a.PH, a.PW);
+  else stage_tile<true>(a, a.x32, st, bs, chunk, y0 - 3, x0 - 3, a.PH, a.PW, a.PH, a.PW);
   __syncthreads();
   const int g = threadIdx.x & 7, strip = threadIdx.x >> 3, gg = chunk * 8 + g;
   if (strip >= a.TH * a.segs || gg >= a.G) return;
@@ -142,7 +154,7 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const DwArgs a) {
   for (int r = 0; r < 7; ++r) {
     const int ox = x0 + sx + r;
     if (ox >= a.W || sx + r >= a.TW) continue;
-    const long e = (((long)b * a.H + oy) * a.W + ox) * a.C + gg * 8;
+    const long e = (((long)(BWD ? bs : b) * a.H + oy) * a.W + ox) * a.C + gg * 8;
     if (!BWD) {
       float o[8];
 #pragma unroll
@@ -169,7 +181,7 @@ __global__ __launch_bounds__(256) void dwconv7_kernel(const DwArgs a) {
 // slot, slot + 4, ... of every tile its workgroup visits (grid-stride over (b, tile)).  The four
 // slots are then summed in slot order through LDS and the workgroup writes one [50][64] partial
 // (row 49 = the bias gradient, gathered by the ky = 0 threads).
-template <int P, int T>
+template <int P, int T, bool IDX = false>
 __global__ __launch_bounds__(256) void dwconv7_bwd_weight_kernel(const DwArgs a) {
   __shared__ uint4 sx[P * P * 8];
   __shared__ uint4 sd[T * T * 8];
@@ -188,8 +200,10 @@ __global__ __launch_bounds__(256) void dwconv7_bwd_weight_kernel(const DwArgs a)
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
     const int b = item / ntiles, tile = item - b * ntiles;
     const int y0 = (tile / a.tiles_x) * a.TH, x0 = (tile % a.tiles_x) * a.TW;
+    const int bs = IDX ? a.idx[b] : b;
+    if (IDX && (unsigned)bs >= (unsigned)a.planes) continue;  // uniform over the workgroup
     __syncthreads();  // the previous item's readers are done
-    stage_tile<true>(a, a.x32, sx, b, chunk, y0 - 3, x0 - 3, a.PH, a.PW, a.PH, a.PW);
+    stage_tile<true>(a, a.x32, sx, bs, chunk, y0 - 3, x0 - 3, a.PH, a.PW, a.PH, a.PW);
     stage_tile<false>(a, a.x16, sd, b, chunk, y0, x0, a.TH, DW, a.TH, a.TW);
     __syncthreads();
     if (slot < 4 && gg < a.G)
@@ -345,6 +359,88 @@ __global__ __launch_bounds__(256) void colsum_partials_kernel(int C, int nb, con
   float s = 0.f;
   for (int n = 0; n < nb; ++n) s += partials[(long)n * C + c];
   dst[c] += s;
+}
+
+// ConvNextDropPath on the layer-scale residual: r + (g*y)*s with the two products and the sum
+// each rounded to fp32 (torch: mul, div by the scalar keep_prob = a mul by s, add).
+__device__ __forceinline__ float mul_mul_add3(float r, float g, float y, float s) {
+#pragma clang fp contract(off)
+  const float p = g * y;
+  const float q = p * s;
+  return r + q;
+}
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return p;
+}
+
+// One pass over the dense stream: a kept plane (slot[b] >= 0, its branch at compact plane slot[b])
+// gets the rule above, a dropped plane is copied.
+__global__ __launch_bounds__(256) void droppath_add_kernel(long rows, int rps, int C, int kept,
+                                                           const float* resid,
+                                                           const float* __restrict__ gamma,
+                                                           const bf16_t* __restrict__ y, long ld_y,
+                                                           const int* __restrict__ slot, float s,
+                                                           float* out) {
+  const int G = C >> 3;
+  const long n = rows * G;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long r = i / G;
+    const int g = (int)(i - r * G);
+    const long b = r / rps;
+    const int sl = slot[b];
+    float o[8];
+    ld8f(resid + r * C + g * 8, o);
+    if (sl >= 0 && sl < kept) {
+      const long ry = (long)sl * rps + (r - b * rps);
+      float yf[8], gm[8];
+      unpack8(*(const uint4*)(y + ry * ld_y + g * 8), yf);
+      ld8f(gamma + g * 8, gm);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) o[c] = mul_mul_add3(o[c], gm[c], yf[c], s);
+    }
+    st8f(out + r * C + g * 8, o);
+  }
+}
+
+// layerscale_bwd_kernel over the kept samples: compact row r reads g at plane idx[r / rps], with
+// g' = g*s (rounded to fp32) in the place of g.
+__global__ __launch_bounds__(256) void droppath_bwd_kernel(long rows, int rps, int C, int planes,
+                                                           const float* __restrict__ gr,
+                                                           const int* __restrict__ idx,
+                                                           const float* __restrict__ gamma,
+                                                           const bf16_t* __restrict__ y, long ld_y,
+                                                           float sc, bf16_t* dy, long ld_dy,
+                                                           float* partials) {
+  __shared__ float red[RS_SLOTS][32][8];
+  const int gl = threadIdx.x & 31, slot = threadIdx.x >> 5;
+  const int g = blockIdx.x * 32 + gl, G = C >> 3;
+  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (g < G) {
+    float gm[8];
+    ld8f(gamma + g * 8, gm);
+    for (long r = (long)blockIdx.y * RS_SLOTS + slot; r < rows; r += (long)gridDim.y * RS_SLOTS) {
+      const long b = r / rps;
+      const int bs = idx[b];
+      if ((unsigned)bs >= (unsigned)planes) continue;
+      const long rg = (long)bs * rps + (r - b * rps);
+      float gv[8], yf[8], o[8];
+      ld8f(gr + rg * C + g * 8, gv);
+      unpack8(*(const uint4*)(y + r * ld_y + g * 8), yf);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const float gp = mul_rn(gv[c], sc);
+        o[c] = gm[c] * gp;
+        s[c] = fmaf(gp, yf[c], s[c]);
+      }
+      *(uint4*)(dy + r * ld_dy + g * 8) = pack8(o);
+    }
+  }
+  slot_sum(red, slot, gl, s);
+  if (slot == 0 && g < G) {
+    st8f(partials + (long)blockIdx.y * C + g * 8, s);
+  }
 }
 
 // p[b][c] = (Σ_hw x[b][hw][c]) * (1 / HW): one workgroup per (256 channels, image).  The scale is
@@ -515,6 +611,138 @@ extern "C" int mmpt_dwconv7_bwd_weight(int64_t B, int64_t H, int64_t W, int64_t 
   dwconv7_reduce_kernel<<<(unsigned)((50 * C + 255) / 256), 256, 0, (hipStream_t)stream>>>(
       (int)C, a.nb, a.partials, dw, db);
   return check_launch("dwconv7_bwd_weight");
+}
+
+// ---- stochastic depth: the sample-indexed forms and the drop-path residual ---------------------
+#define MMPT_CN_KEPT(what)                                                                    \
+  MMPT_REQUIRE(Bk >= 1 && Bk <= B, what ": 1 <= Bk <= B (Bk %lld, B %lld)", (long long)Bk, \
+               (long long)B)
+#define MMPT_CN_P(what) \
+  MMPT_REQUIRE(p >= 0.0 && p < 1.0, what ": p must lie in [0, 1), got %g", p)
+inline bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
+extern "C" int mmpt_dwconv7_idx_fwd(int64_t B, int64_t Bk, int64_t H, int64_t W, int64_t C,
+                                    const float* x, const void* idx, const void* w,
+                                    const void* bias, void* c, void* stream) {
+  MMPT_CN_PLANE("dwconv7_idx_fwd");
+  MMPT_CN_KEPT("dwconv7_idx_fwd");
+  MMPT_REQUIRE(x && idx && w && bias && c, "dwconv7_idx_fwd: null pointer");
+  MMPT_REQUIRE(al16(x) && al16(w) && al16(bias) && al16(c) && al4(idx),
+               "dwconv7_idx_fwd: pointers must be 16-byte aligned (idx: 4-byte)");
+  DwArgs a = {};
+  dw_geometry(a, Bk, H, W, C);
+  a.x32 = x; a.w = (const bf16_t*)w; a.bias = (const bf16_t*)bias; a.o16 = (bf16_t*)c;
+  a.idx = (const int*)idx; a.planes = (int)B;
+  const dim3 grid((unsigned)(Bk * a.tiles_y * a.tiles_x), (unsigned)dw_chunks(a));
+  const unsigned threads = (unsigned)((8 * a.TH * a.segs + 63) / 64 * 64);
+  if (a.TH <= 7 && a.TW <= 7)
+    dwconv7_kernel<false, 13, true><<<grid, threads, 0, (hipStream_t)stream>>>(a);
+  else
+    dwconv7_kernel<false, DW_P, true><<<grid, threads, 0, (hipStream_t)stream>>>(a);
+  return check_launch("dwconv7_idx_fwd");
+}
+
+extern "C" int mmpt_dwconv7_idx_bwd_input(int64_t B, int64_t Bk, int64_t H, int64_t W, int64_t C,
+                                          const void* dc, const void* idx, const void* w,
+                                          const float* dx_in, float* dx_out, void* stream) {
+  MMPT_CN_PLANE("dwconv7_idx_bwd_input");
+  MMPT_CN_KEPT("dwconv7_idx_bwd_input");
+  MMPT_REQUIRE(dc && idx && w && dx_out, "dwconv7_idx_bwd_input: null pointer");
+  MMPT_REQUIRE(al16(dc) && al16(w) && al16(dx_in) && al16(dx_out) && al4(idx),
+               "dwconv7_idx_bwd_input: pointers must be 16-byte aligned (idx: 4-byte)");
+  DwArgs a = {};
+  dw_geometry(a, Bk, H, W, C);
+  a.x16 = (const bf16_t*)dc; a.w = (const bf16_t*)w; a.r32 = dx_in; a.o32 = dx_out;
+  a.idx = (const int*)idx; a.planes = (int)B;
+  const dim3 grid((unsigned)(Bk * a.tiles_y * a.tiles_x), (unsigned)dw_chunks(a));
+  const unsigned threads = (unsigned)((8 * a.TH * a.segs + 63) / 64 * 64);
+  if (a.TH <= 7 && a.TW <= 7)
+    dwconv7_kernel<true, 13, true><<<grid, threads, 0, (hipStream_t)stream>>>(a);
+  else
+    dwconv7_kernel<true, DW_P, true><<<grid, threads, 0, (hipStream_t)stream>>>(a);
+  return check_launch("dwconv7_idx_bwd_input");
+}
+
+extern "C" int mmpt_dwconv7_idx_bwd_weight(int64_t B, int64_t Bk, int64_t H, int64_t W, int64_t C,
+                                           const float* x, const void* idx, const void* dc,
+                                           float* dw, float* db, void* workspace, void* stream) {
+  MMPT_CN_PLANE("dwconv7_idx_bwd_weight");
+  MMPT_CN_KEPT("dwconv7_idx_bwd_weight");
+  MMPT_REQUIRE(x && idx && dc && dw && db && workspace, "dwconv7_idx_bwd_weight: null pointer");
+  MMPT_REQUIRE(al16(x) && al16(dc) && al16(dw) && al16(db) && al16(workspace) && al4(idx),
+               "dwconv7_idx_bwd_weight: pointers must be 16-byte aligned (idx: 4-byte)");
+  DwArgs a = {};
+  dw_geometry(a, Bk, H, W, C);
+  a.x32 = x; a.x16 = (const bf16_t*)dc; a.partials = (float*)workspace; a.nb = (int)dw_nb(a);
+  a.idx = (const int*)idx; a.planes = (int)B;
+  const dim3 grid((unsigned)a.nb, (unsigned)dw_chunks(a));
+  if (a.TH <= 7 && a.TW <= 7)
+    dwconv7_bwd_weight_kernel<13, 7, true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  else
+    dwconv7_bwd_weight_kernel<DW_P, DW_T, true><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+  int rc = check_launch("dwconv7_idx_bwd_weight");
+  if (rc) return rc;
+  dwconv7_reduce_kernel<<<(unsigned)((50 * C + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      (int)C, a.nb, a.partials, dw, db);
+  return check_launch("dwconv7_idx_bwd_weight");
+}
+
+#define MMPT_CN_SAMPLES(what)                                                                    \
+  MMPT_REQUIRE(B > 0 && rows_per_sample > 0 && B < ((int64_t)1 << 31) &&                         \
+                   rows_per_sample < ((int64_t)1 << 31) &&                                       \
+                   B * rows_per_sample < ((int64_t)1 << 31) && C > 0 && C % 8 == 0 && C <= 4096, \
+               what ": B, rows_per_sample >= 1 with B*rows_per_sample < 2^31, C a positive "    \
+                    "multiple of 8 and <= 4096 (B %lld, rows_per_sample %lld, C %lld)",          \
+               (long long)B, (long long)rows_per_sample, (long long)C)
+
+extern "C" int mmpt_droppath_add_fwd(int64_t B, int64_t Bk, int64_t rows_per_sample, int64_t C,
+                                     const float* resid, const float* gamma, const void* y,
+                                     int64_t ld_y, const void* slot, double p, float* out,
+                                     void* stream) {
+  MMPT_CN_SAMPLES("droppath_add_fwd");
+  MMPT_REQUIRE(Bk >= 0 && Bk <= B, "droppath_add_fwd: 0 <= Bk <= B (Bk %lld, B %lld)",
+               (long long)Bk, (long long)B);
+  MMPT_CN_P("droppath_add_fwd");
+  MMPT_REQUIRE(resid && gamma && slot && out && (y || Bk == 0), "droppath_add_fwd: null pointer");
+  if (Bk > 0) MMPT_CN_LD("droppath_add_fwd", ld_y);
+  MMPT_REQUIRE(al16(resid) && al16(gamma) && al16(y) && al16(out) && al4(slot),
+               "droppath_add_fwd: pointers must be 16-byte aligned (slot: 4-byte)");
+  const int64_t rows = B * rows_per_sample;
+  droppath_add_kernel<<<blocks_for(rows * (C / 8)), 256, 0, (hipStream_t)stream>>>(
+      rows, (int)rows_per_sample, (int)C, (int)Bk, resid, gamma, (const bf16_t*)y, ld_y,
+      (const int*)slot, dropout_scale(p), out);
+  return check_launch("droppath_add_fwd");
+}
+
+extern "C" int64_t mmpt_droppath_bwd_workspace_bytes(int64_t Bk, int64_t rows_per_sample,
+                                                     int64_t C) {
+  return mmpt_layerscale_bwd_workspace_bytes(Bk * rows_per_sample, C);
+}
+
+extern "C" int mmpt_droppath_bwd(int64_t B, int64_t Bk, int64_t rows_per_sample, int64_t C,
+                                 const float* g, const void* idx, const float* gamma,
+                                 const void* y, int64_t ld_y, double p, void* dy, int64_t ld_dy,
+                                 float* dgamma, void* workspace, void* stream) {
+  MMPT_CN_SAMPLES("droppath_bwd");
+  MMPT_CN_KEPT("droppath_bwd");
+  MMPT_CN_P("droppath_bwd");
+  MMPT_CN_LD("droppath_bwd", ld_y);
+  MMPT_CN_LD("droppath_bwd", ld_dy);
+  MMPT_REQUIRE(g && idx && gamma && y && dy && dgamma && workspace, "droppath_bwd: null pointer");
+  MMPT_REQUIRE(al16(g) && al16(gamma) && al16(y) && al16(dy) && al16(dgamma) && al16(workspace) &&
+                   al4(idx),
+               "droppath_bwd: pointers must be 16-byte aligned (idx: 4-byte)");
+  const int64_t rows = Bk * rows_per_sample;
+  const int nb = (int)std::min<int64_t>(RS_BLOCKS, (rows + RS_SLOTS - 1) / RS_SLOTS);
+  const dim3 grid((unsigned)((C / 8 + 31) / 32), (unsigned)nb);
+  droppath_bwd_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(
+      rows, (int)rows_per_sample, (int)C, (int)B, g, (const int*)idx, gamma, (const bf16_t*)y,
+      ld_y, dropout_scale(p), (bf16_t*)dy, ld_dy, (float*)workspace);
+  int rc = check_launch("droppath_bwd");
+  if (rc) return rc;
+  colsum_partials_kernel<<<(unsigned)((C + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      (int)C, nb, (const float*)workspace, dgamma);
+  return check_launch("droppath_bwd");
 }
 
 extern "C" int mmpt_layerscale_add_fwd(int64_t rows, int64_t C, const float* resid,

@@ -46,6 +46,7 @@ import torch
 
 from . import kernels as K
 from .config import ModelConfig
+from .droppath import kept_indices_of
 from .params import ParamStore
 
 BF16 = torch.bfloat16
@@ -104,6 +105,8 @@ def sort_segments(ids: np.ndarray, rows: np.ndarray):
 # VISION_UNIT + 1 + i = ViT layer i (so at most 2047 layers a side); k: the site inside the
 # unit (a layer: 0 = after the attention output projection, 1 = after the MLP, 2 = the
 # attention probabilities — the site of the mmpt_attention_drop_* calls, which share the seed).
+# ConvNeXt: VISION_UNIT + 1 + j = block j counted over all stages, k = 3 = its drop-path bits
+# (element b = sample b; the blocks have no other site).
 SITE_STEPS, SITE_RANKS, SITE_UNITS, SITE_KS = 1 << 32, 1 << 16, 1 << 12, 1 << 4
 VISION_UNIT = SITE_UNITS // 2
 
@@ -575,6 +578,13 @@ class Engine:
                 raise ValueError(f"{layers} layers: dropout_site numbers at most {VISION_UNIT - 1}")
         self._pt = self._pv = 0.0  # the probabilities of the micro-step in flight
         self._pat = self._pav = 0.0  # ... of the attention-probability dropout (text, vision)
+        # ConvNeXt stochastic depth (cfg.convnext.drop_path_rate): the per-block rates of the
+        # micro-step in flight (None: the dense path) and its blocks' kept samples
+        self._pdp = None
+        self._kept: dict = {}
+        if cfg.convnext is not None and sum(cfg.convnext.depths) >= VISION_UNIT:
+            raise ValueError(f"{sum(cfg.convnext.depths)} blocks: dropout_site numbers at most "
+                             f"{VISION_UNIT - 1}")
         self._dstep = 0
         if store.device.type == "cuda":
             store.refresh_transposed()
@@ -826,7 +836,13 @@ class Engine:
         self._pav = self.cfg.vision.attention_dropout if on and self.cfg.multimodal and \
             not self.frozen else 0.0
         self._dstep = self.dropout_step
-        if need_grad and max(self._pt, self._pv, self._pat, self._pav) > 0:
+        # stochastic depth is training only: a forward without gradients runs every block densely
+        cn = self.cfg.convnext
+        self._pdp = cn.drop_path_rates() if on and need_grad and cn is not None and \
+            cn.drop_path_rate > 0 else None
+        self._kept = {}
+        if need_grad and (max(self._pt, self._pv, self._pat, self._pav) > 0 or
+                          self._pdp is not None):
             self.dropout_step += 1
 
     def _drop_grad(self, d, p, unit, k, bias, out=None):
@@ -1275,13 +1291,79 @@ class Engine:
     # The residual stream x is fp32 [B·H·W, C], channels-last.  A block keeps (x, c, mean, rstd,
     # n, pre, act, y) for its backward; with activation checkpointing a STAGE keeps only its
     # input and is recomputed before its backward (the reference's
-    # ConvNextEncoderWithCheckpointing wraps each ConvNextStage).
+    # ConvNextEncoderWithCheckpointing wraps each ConvNextStage).  Stochastic depth
+    # (drop_path_rate > 0, training): a block with drop probability > 0 runs over its kept samples
+    # only (_cn_block_drop_fwd / _bwd) and additionally keeps their map and its probability.
     def _cn_f32_of_bf16(self, x, name):
         """f32(bf16(x·Wᵀ + b)): a conv output (bf16 under autocast) held exactly in the fp32
         stream — the residual epilogue over a zero residual."""
         W = self.s.w(name + ".weight")
         zero = torch.zeros(x.shape[0], W.shape[0], dtype=F32, device=self.dev)
         return self._linear(x, name, epi=K.EPI_F32_RESID, out2=zero)
+
+    def _cn_kept(self, j, B):
+        """Block j's kept samples under stochastic depth, decided on the host: the keep bits of
+        site (micro-step, rank, VISION_UNIT + 1 + j, 3), elements 0 .. B-1.  The tables of every
+        block of the micro-step are drawn on first use and go to the device in one copy; a
+        recompute under activation checkpointing finds them again."""
+        if not self._kept:
+            js = [i for i, p in enumerate(self._pdp) if p > 0]
+            idxs = kept_indices_of(B, [self._pdp[i] for i in js], self.dropout_seed,
+                                   [self._site(VISION_UNIT + 1 + i, 3) for i in js])
+            self._kept = dict(zip(js, K.kept_samples_of(B, idxs, self.dev)))
+        return self._kept[j]
+
+    def _cn_block_drop_fwd(self, p, x, B, side, j):
+        """_cn_block_fwd over the kept samples of block j (drop probability > 0): the branch is
+        computed for them alone, compactly; dropped planes of x are copied.  Nobody kept: the
+        block is the identity and saves nothing."""
+        kept, pj = self._cn_kept(j, B), self._pdp[j]
+        if kept.Bk == 0:
+            return x, None
+        R, C = x.shape
+        rps = side * side
+        Rk = kept.Bk * rps
+        c = self._e(Rk, C)
+        K.dwconv7_idx_fwd(x.view(B, side, side, C), kept, self.s.w(p + "dw.weight"),
+                          self.s.w(p + "dw.bias"), c.view(kept.Bk, side, side, C))
+        n = self._e(Rk, C)
+        m, r = self._e(Rk, dtype=F32), self._e(Rk, dtype=F32)
+        K.mlm_ln_fwd(c, self.s.p(p + "ln.weight"), self.s.p(p + "ln.bias"), self.cfg.convnext.eps,
+                     n, m, r)
+        pre, act = self._e(Rk, 4 * C), self._e(Rk, 4 * C)
+        self._linear(n, p + "fc1", out=pre, epi=K.EPI_BF16_GELU, out2=act)
+        y = self._linear(act, p + "fc2")
+        xn = self._e(R, C, dtype=F32)
+        K.droppath_add_fwd(x.view(B, rps, C), self.s.p(p + "gamma"), y, kept, pj,
+                           xn.view(B, rps, C))
+        return xn, (x, c, m, r, n, pre, act, y, kept, pj)
+
+    def _cn_block_drop_bwd(self, p, g, saved, B, side):
+        """Backward of _cn_block_drop_fwd: only the kept planes of g change; a block that kept
+        nobody (saved None) leaves g and its parameter gradients untouched."""
+        if saved is None:
+            return g
+        x, c, m, r, n, pre, act, y, kept, pj = saved
+        R, C = x.shape
+        rps = side * side
+        Rk = kept.Bk * rps
+        self._side_fence()
+        dy = self._e(Rk, C)
+        K.droppath_bwd(g.view(B, rps, C), kept, self.s.p(p + "gamma"), y, pj, dy,
+                       self.s.g(p + "gamma"))
+        dpre = self._dx_dgelu(dy, p + "fc2", pre, bias_of=p + "fc1")
+        self._dw(dy, act, p + "fc2")
+        dn = self._dx(dpre, p + "fc1")
+        self._dw(dpre, n, p + "fc1", bias=False)
+        dc = self._e(Rk, C)
+        K.ln16_bwd(c, m, r, self.s.p(p + "ln.weight"), dn, dc, dw=self.s.g(p + "ln.weight"),
+                   db=self.s.g(p + "ln.bias"))
+        dc4 = dc.view(kept.Bk, side, side, C)
+        K.dwconv7_idx_bwd_weight(x.view(B, side, side, C), kept, dc4, self.s.g(p + "dw.weight"),
+                                 self.s.g(p + "dw.bias"))
+        g4 = g.view(B, side, side, C)
+        K.dwconv7_idx_bwd_input(dc4, kept, self.s.w(p + "dw.weight"), g4, dx_in=g4)
+        return g
 
     def _cn_block_fwd(self, p, x, B, side):
         """ConvNextLayer under autocast: x + gamma * f32(fc2(gelu(fc1(LN(dwconv(bf16 x))))))."""
@@ -1339,8 +1421,12 @@ class Engine:
             down = (x, m, r, rows)
             x = self._cn_f32_of_bf16(rows, p + "down")
         blocks = []
+        j0 = sum(cn.depths[:s])  # block numbers count over all stages (the drop-path rates)
         for j in range(cn.depths[s]):
-            x, saved = self._cn_block_fwd(f"{p}layers.{j}.", x, B, side)
+            if self._pdp is not None and self._pdp[j0 + j] > 0:
+                x, saved = self._cn_block_drop_fwd(f"{p}layers.{j}.", x, B, side, j0 + j)
+            else:
+                x, saved = self._cn_block_fwd(f"{p}layers.{j}.", x, B, side)
             blocks.append(saved)
         if ckpt:
             self.cache[("cn", s)] = ("ckpt", x_in)
@@ -1355,8 +1441,12 @@ class Engine:
         self._unit_bwd(f"convnext.stages.{s}")
         self._restore(("cn", s), self._cn_stage_fwd, s, B, None)
         down, blocks = self.cache.pop(("cn", s))
+        j0 = sum(cn.depths[:s])
         for j in reversed(range(cn.depths[s])):
-            g = self._cn_block_bwd(f"{p}layers.{j}.", g, blocks.pop(), B, side)
+            if self._pdp is not None and self._pdp[j0 + j] > 0:
+                g = self._cn_block_drop_bwd(f"{p}layers.{j}.", g, blocks.pop(), B, side)
+            else:
+                g = self._cn_block_bwd(f"{p}layers.{j}.", g, blocks.pop(), B, side)
         if down is not None:
             x, m, r, rows = down
             Cin, sin = cn.hidden_sizes[s - 1], cn.side(s - 1)

@@ -948,6 +948,148 @@ def layerscale_bwd(g, gamma, y, dy, dgamma) -> None:
               dy.data_ptr(), ld_dy, dgamma.data_ptr(), ws.data_ptr(), _stream())
 
 
+# Stochastic depth (include/mmpt.h "K21 stochastic depth"): a block runs over its kept samples.
+class KeptSamples:
+    """The kept samples of one block: `B` planes in the fp32 stream, host `idx` (the kept planes,
+    a tuple), `Bk`, and the device int32 tables `idx_dev` [Bk] (compact -> plane) and `slot_dev`
+    [B] (plane -> compact, -1 where dropped).  Async copies on the current stream; nothing is
+    read back.  `tables`: the two device tables already made (kept_samples_of: one copy for many
+    blocks).  The wrappers check the host copy before every launch."""
+
+    def __init__(self, B: int, idx, device, tables=None):
+        self.B, self.idx = int(B), tuple(int(i) for i in idx)
+        self.Bk = len(self.idx)
+        if tables is None:
+            both = torch.tensor(self.idx + self.slots(), dtype=torch.int32)
+            both = both.to(torch.device(device), non_blocking=True)
+            tables = both[:self.Bk], both[self.Bk:]
+        self.idx_dev, self.slot_dev = tables
+        self.checked = None
+
+    def slots(self) -> tuple:
+        slot = [-1] * self.B
+        for k, i in enumerate(self.idx):
+            if 0 <= i < self.B:
+                slot[i] = k
+        return tuple(slot)
+
+
+def kept_samples_of(B: int, idxs, device) -> list:
+    """KeptSamples for several blocks at once (`idxs`: one index tuple per block): every table in
+    one buffer, staged in pinned memory and copied by one asynchronous copy on the current
+    stream, so drawing a micro-step's masks costs neither a launch per block nor a wait."""
+    device = torch.device(device)
+    ks = [KeptSamples(B, idx, device, tables=(None, None)) for idx in idxs]
+    flat = [v for k in ks for v in k.idx + k.slots()]
+    host = torch.tensor(flat, dtype=torch.int32)
+    if device.type == "cuda":
+        host = host.pin_memory()
+    dev = host.to(device, non_blocking=True)
+    o = 0
+    for k in ks:
+        k.idx_dev, k.slot_dev = dev[o:o + k.Bk], dev[o + k.Bk:o + k.Bk + B]
+        o += k.Bk + B
+    return ks
+
+
+def _kept(kept: KeptSamples, B: int, name: str, empty_ok: bool = False) -> None:
+    idx = kept.idx
+    if kept.B != B:
+        raise ValueError(f"{name}: the sample map is over {kept.B} planes, the stream has {B}")
+    if not idx and not empty_ok:
+        raise ValueError(f"{name}: no kept sample (1 <= Bk <= B)")
+    if kept.checked is idx:  # the host copy is a tuple: one walk per map, not one per launch
+        return
+    if any(not 0 <= i < B for i in idx) or any(a >= b for a, b in zip(idx, idx[1:])):
+        raise ValueError(f"{name}: idx must be strictly increasing within [0, {B}), got {idx}")
+    if tuple(kept.idx_dev.shape) != (len(idx),) or tuple(kept.slot_dev.shape) != (B,) or \
+            kept.idx_dev.dtype != torch.int32 or kept.slot_dev.dtype != torch.int32:
+        raise ValueError(f"{name}: the device tables do not match the host copy")
+    kept.checked = idx
+
+
+def _check_p(p: float, name: str) -> float:
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name}: p must lie in [0, 1), got {p!r}")
+    return float(p)
+
+
+def dwconv7_idx_fwd(x, kept: KeptSamples, w, bias, c) -> None:
+    """dwconv7_fwd over the kept planes: c[b'] = conv(x[idx[b']]); x fp32 [B, H, W, C] read through
+    the map, c bf16 compact [Bk, H, W, C]."""
+    B, H, W, C = _nhwc(x, torch.float32, "dwconv7_idx_fwd.x")
+    _kept(kept, B, "dwconv7_idx_fwd")
+    _nhwc(c, torch.bfloat16, "dwconv7_idx_fwd.c", (kept.Bk, H, W, C))
+    _dense(w, torch.bfloat16, (49, C), "dwconv7_idx_fwd.w")
+    _dense(bias, torch.bfloat16, (C,), "dwconv7_idx_fwd.bias")
+    _lib.call("mmpt_dwconv7_idx_fwd", B, kept.Bk, H, W, C, x.data_ptr(), kept.idx_dev.data_ptr(),
+              w.data_ptr(), bias.data_ptr(), c.data_ptr(), _stream())
+
+
+def dwconv7_idx_bwd_input(dc, kept: KeptSamples, w, dx_out, dx_in=None) -> None:
+    """dx_out[idx[b']] = dx_in[idx[b']] + f32(bf16(dwconv7x7^T(dc[b']; w))): only the mapped planes
+    of the dense fp32 [B, H, W, C] stream are touched; dc bf16 compact [Bk, H, W, C]."""
+    B, H, W, C = _nhwc(dx_out, torch.float32, "dwconv7_idx_bwd_input.dx_out")
+    _kept(kept, B, "dwconv7_idx_bwd_input")
+    _nhwc(dc, torch.bfloat16, "dwconv7_idx_bwd_input.dc", (kept.Bk, H, W, C))
+    if dx_in is not None:
+        _nhwc(dx_in, torch.float32, "dwconv7_idx_bwd_input.dx_in", (B, H, W, C))
+    _dense(w, torch.bfloat16, (49, C), "dwconv7_idx_bwd_input.w")
+    _lib.call("mmpt_dwconv7_idx_bwd_input", B, kept.Bk, H, W, C, dc.data_ptr(),
+              kept.idx_dev.data_ptr(), w.data_ptr(), _p(dx_in), dx_out.data_ptr(), _stream())
+
+
+def dwconv7_idx_bwd_weight(x, kept: KeptSamples, dc, dw, db) -> None:
+    """dwconv7_bwd_weight over the kept planes: x fp32 [B, H, W, C] through the map, dc compact."""
+    B, H, W, C = _nhwc(x, torch.float32, "dwconv7_idx_bwd_weight.x")
+    _kept(kept, B, "dwconv7_idx_bwd_weight")
+    _nhwc(dc, torch.bfloat16, "dwconv7_idx_bwd_weight.dc", (kept.Bk, H, W, C))
+    _dense(dw, torch.float32, (49, C), "dwconv7_idx_bwd_weight.dw")
+    _dense(db, torch.float32, (C,), "dwconv7_idx_bwd_weight.db")
+    ws = workspace(_lib.query("mmpt_dwconv7_bwd_weight_workspace_bytes", kept.Bk, H, W, C), slot=2)
+    _lib.call("mmpt_dwconv7_idx_bwd_weight", B, kept.Bk, H, W, C, x.data_ptr(),
+              kept.idx_dev.data_ptr(), dc.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
+              _stream())
+
+
+def droppath_add_fwd(resid, gamma, y, kept: KeptSamples, p: float, out) -> None:
+    """ConvNextDropPath on the residual, one pass: a kept plane b gets resid + s * (gamma *
+    f32(y[slot[b]])) (three fp32 roundings, s = float(1 / (1 - p))), a dropped plane is copied.
+    resid / out fp32 [B, rows_per_sample, C] (out may be resid); y bf16 [Bk * rows_per_sample, C]
+    (None when nobody is kept)."""
+    _check(resid, torch.float32, "droppath_add_fwd.resid")
+    if resid.dim() != 3 or not resid.is_contiguous():
+        raise ValueError("droppath_add_fwd.resid: expected a dense [B, rows_per_sample, C] tensor")
+    B, rps, C = resid.shape
+    _kept(kept, B, "droppath_add_fwd", empty_ok=True)
+    _dense(out, torch.float32, (B, rps, C), "droppath_add_fwd.out")
+    _dense(gamma, torch.float32, (C,), "droppath_add_fwd.gamma")
+    p = _check_p(p, "droppath_add_fwd")
+    ld_y = _rows_bf16(y, kept.Bk * rps, C, "droppath_add_fwd.y") if kept.Bk else 0
+    _lib.call("mmpt_droppath_add_fwd", B, kept.Bk, rps, C, resid.data_ptr(), gamma.data_ptr(),
+              _p(y) if kept.Bk else None, ld_y, kept.slot_dev.data_ptr(), p, out.data_ptr(),
+              _stream())
+
+
+def droppath_bwd(g, kept: KeptSamples, gamma, y, p: float, dy, dgamma) -> None:
+    """layerscale_bwd over the kept samples with g' = g * s: dy = bf16(gamma * g') compact,
+    dgamma += Σ g' * f32(y) over the kept rows; g fp32 [B, rows_per_sample, C] read through idx."""
+    _check(g, torch.float32, "droppath_bwd.g")
+    if g.dim() != 3 or not g.is_contiguous():
+        raise ValueError("droppath_bwd.g: expected a dense [B, rows_per_sample, C] tensor")
+    B, rps, C = g.shape
+    _kept(kept, B, "droppath_bwd")
+    _dense(gamma, torch.float32, (C,), "droppath_bwd.gamma")
+    _dense(dgamma, torch.float32, (C,), "droppath_bwd.dgamma")
+    p = _check_p(p, "droppath_bwd")
+    ld_y = _rows_bf16(y, kept.Bk * rps, C, "droppath_bwd.y")
+    ld_dy = _rows_bf16(dy, kept.Bk * rps, C, "droppath_bwd.dy")
+    ws = workspace(_lib.query("mmpt_droppath_bwd_workspace_bytes", kept.Bk, rps, C), slot=2)
+    _lib.call("mmpt_droppath_bwd", B, kept.Bk, rps, C, g.data_ptr(), kept.idx_dev.data_ptr(),
+              gamma.data_ptr(), y.data_ptr(), ld_y, p, dy.data_ptr(), ld_dy, dgamma.data_ptr(),
+              ws.data_ptr(), _stream())
+
+
 def ln16_bwd(c, mean, rstd, w, dn16, dc, dw=None, db=None) -> None:
     """dc = bf16(LN'(f32(dn16); f32(c))): the backward of mlm_ln_fwd; dw / db +=."""
     rows, h = c.shape

@@ -529,8 +529,9 @@ class MMPTForPretraining(nn.Module):
 
     def set_dropout_seed(self, seed: int) -> None:
         """Key of the hidden- and attention-dropout masks (cfg.text / cfg.vision
-        .hidden_dropout, text.attn_dropout, vision.attention_dropout; default: the
-        constructor's `seed`).  Dropout is active iff the module is in train() mode and p > 0;
+        .hidden_dropout, text.attn_dropout, vision.attention_dropout) and of ConvNeXt's
+        stochastic-depth keep bits (cfg.convnext.drop_path_rate); default: the constructor's
+        `seed`.  Each is active iff the module is in train() mode and its p > 0;
         the masks also depend on the micro-step counter and the data-parallel rank
         (engine.dropout_site)."""
         self.engine.dropout_seed = int(seed)
@@ -617,7 +618,8 @@ def build_hf_model(cfg: C.ModelConfig) -> nn.Module:
             num_channels=cn.channels, patch_size=cn.patch, num_stages=4,
             hidden_sizes=list(cn.hidden_sizes), depths=list(cn.depths), hidden_act="gelu",
             initializer_range=0.02, layer_norm_eps=cn.head_eps,
-            layer_scale_init_value=cn.layer_scale_init, drop_path_rate=0.0, image_size=cn.image,
+            layer_scale_init_value=cn.layer_scale_init, drop_path_rate=cn.drop_path_rate,
+            image_size=cn.image,
             num_labels=cfg.num_classes))
     if cfg.classifier:
         from transformers import ViTConfig, ViTForImageClassification

@@ -348,6 +348,28 @@ int mmpt_embed_bwd(int64_t rows, int64_t h, int64_t nseg, const int32_t* seg_id,
                    const int32_t* seg_off, const int32_t* perm, const int32_t* img_map,
                    const float* dout, float* dtable, void* dimg, void* stream);
 
+/* K8 with NEFTune noise (TrainingArguments.neftune_noise_alpha; tf:integrations/neftune.py
+ * neftune_post_forward_hook on the input embedding).  The noise rule (csrc/philox.h, host and
+ * device): logical element e = r*h + col of noise site `site` takes word e % 4 of K16's
+ * dropout_words(e / 4, site, seed);
+ *   k = word >> 9 (23 bits),  s = (float)(2k + 1) * 2^-23 - 1   exact, in (-1, 1), never 0
+ *   noise = fmul_rn(s, mag),  out = fadd_rn(value, noise)       two fp32 roundings, never an fma
+ * mag = alpha / sqrt(S_in * h) computed in double and rounded once to fp32, S_in the width of
+ * input_ids as the batch arrived (HF's output.size(1)); r is the kernel's own row.  Nothing is
+ * stored: whoever needs the noise again (a backward that re-gathers, a recompute) draws it again.
+ *   mmpt_embed_noise_fwd: mmpt_embed_fwd with the noise added to text rows in the same pass;
+ *     rows with img_map[r] >= 0 receive f32(img[img_map[r]]) unchanged (masked_scatter
+ *     overwrites them after the hook).  table / out 16-B aligned.
+ *   mmpt_embed_noise: out[e] = noise of element e, fp32 dense [rows][h] (what mmpt_dropout_mask
+ *     is to the masks).
+ * h % 4 == 0, rows < 2^31, mag finite and >= 0, else MMPT_ERR_ARG before any launch.  Added
+ * without a change of MMPT_ABI_VERSION: the entries are new, nothing existing changed. */
+int mmpt_embed_noise_fwd(int64_t rows, int64_t h, const int64_t* ids, const float* table,
+                         const int32_t* img_map, const void* img, float* out, float mag,
+                         uint64_t seed, uint64_t site, void* stream);
+int mmpt_embed_noise(int64_t rows, int64_t h, float mag, uint64_t seed, uint64_t site, float* out,
+                     void* stream);
+
 /* Device-side segment build for the embedding backward (ABI 8; replaces round 2's host
  * numpy argsort behind the same semantics): key[r] = ids[r] (rows with id == skip_id — the
  * LLaVA image slots, pass -1 for none — and out-of-range ids are excluded), stable counting
@@ -632,6 +654,27 @@ int mmpt_roberta_embed_bwd(int64_t rows, int64_t h, const int64_t* ids, const in
                            const float* rstd, const float* w, const float* dh, const void* dhb,
                            float* de, float* dw, float* db, float* dtype, double p, uint64_t seed,
                            uint64_t site, void* workspace, void* stream);
+/* The two entries above with NEFTune noise (K8's rule under noise_seed / noise_site) on
+ * the word row, HF's order since the hook sits on word_embeddings:
+ *   e = ((word[ids[r]] + noise) + type_row) + pos_table[pos[r]]
+ * The backward gathers e again and draws the same noise, so dw, db, dtype and de see the
+ * forward's x̂.  Everything else is the entries above, kernel body shared; mag = 0 gives their
+ * bits.  mag finite and >= 0.  Added without a change of MMPT_ABI_VERSION. */
+int mmpt_roberta_embed_noise_fwd(int64_t rows, int64_t h, float eps, const int64_t* ids,
+                                 const int64_t* pos, const float* word, int64_t vocab,
+                                 const float* pos_table, int64_t max_pos, const float* type_row,
+                                 const float* w, const float* b, float* h32, void* h16,
+                                 float* mean, float* rstd, double p, uint64_t seed, uint64_t site,
+                                 float mag, uint64_t noise_seed, uint64_t noise_site,
+                                 void* stream);
+int mmpt_roberta_embed_noise_bwd(int64_t rows, int64_t h, const int64_t* ids, const int64_t* pos,
+                                 const float* word, int64_t vocab, const float* pos_table,
+                                 int64_t max_pos, const float* type_row, const float* mean,
+                                 const float* rstd, const float* w, const float* dh,
+                                 const void* dhb, float* de, float* dw, float* db, float* dtype,
+                                 double p, uint64_t seed, uint64_t site, float mag,
+                                 uint64_t noise_seed, uint64_t noise_site, void* workspace,
+                                 void* stream);
 /* RobertaLMHead.layer_norm, which reads the bf16 GELU output g [rows][ld_g]:
  *   n16 = bf16(LN(f32(g); w, b, eps))           bf16 [rows][ld_n16]: the decoder's operand
  * (the statistics within an fp32 ulp of mmpt_layernorm_f32_fwd's on f32(g), not its bits) */

@@ -75,6 +75,8 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_dequant_int4_sum": (I32, [I64, I64, P, P, P, P]),
     "mmpt_expand_rows_bf16": (I32, [I64, I64, P, P, I64, P, I64, P]),
     "mmpt_embed_fwd": (I32, [I64, I64, P, P, P, P, P, P]),
+    "mmpt_embed_noise_fwd": (I32, [I64, I64, P, P, P, P, P, F32, U64, U64, P]),
+    "mmpt_embed_noise": (I32, [I64, I64, F32, U64, U64, P, P]),
     "mmpt_embed_bwd": (I32, [I64, I64, I64, P, P, P, P, P, P, P, P]),
     "mmpt_embed_segments_workspace_bytes": (I64, [I64, I64]),
     "mmpt_embed_segments": (I32, [I64, P, I64, I64, P, P, P, P, P, P, I64, P]),
@@ -113,6 +115,8 @@ SIGNATURES: dict[str, tuple] = {
     "mmpt_roberta_embed_fwd": (I32, [I64, I64, F32, P, P, P, I64, P, I64, P, P, P, P, P, P, P, F64, U64, U64, P]),
     "mmpt_roberta_embed_bwd_workspace_bytes": (I64, [I64, I64]),
     "mmpt_roberta_embed_bwd": (I32, [I64, I64, P, P, P, I64, P, I64, P, P, P, P, P, P, P, P, P, P, F64, U64, U64, P, P]),
+    "mmpt_roberta_embed_noise_fwd": (I32, [I64, I64, F32, P, P, P, I64, P, I64, P, P, P, P, P, P, P, F64, U64, U64, F32, U64, U64, P]),
+    "mmpt_roberta_embed_noise_bwd": (I32, [I64, I64, P, P, P, I64, P, I64, P, P, P, P, P, P, P, P, P, P, F64, U64, U64, F32, U64, U64, P, P]),
     "mmpt_mlm_ln_fwd": (I32, [I64, I64, F32, P, I64, P, P, P, I64, P, P, P]),
     "mmpt_mlm_ln_bwd_workspace_bytes": (I64, [I64, I64]),
     "mmpt_mlm_ln_bwd": (I32, [I64, I64, P, I64, P, P, P, P, I64, P, I64, P, I64, P, P, P, P, P]),

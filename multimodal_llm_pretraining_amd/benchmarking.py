@@ -26,7 +26,7 @@ from . import config as C
 from .distributed import sharding_to_mode
 from .optim import AdamConfig, min_lr_rate_of
 from .trainer import ManualTrainer as _StepTrainer
-from .trainer import StepConfig, label_smoothing_from_args
+from .trainer import StepConfig, label_smoothing_from_args, neftune_from_args
 
 logger = logging.getLogger("academic-pretraining")
 
@@ -86,6 +86,10 @@ class ManualTrainer:
                               # HF Trainer wraps the loss in LabelSmoother when the factor is
                               # non-zero; here the cross-entropy kernels smooth
                               label_smoothing=label_smoothing_from_args(
+                                  tc.hf_training_args_overrides, hf_args_overrides),
+                              # HF Trainer hooks the input embedding when the alpha is set; here
+                              # the embedding gather kernels add the noise
+                              neftune_noise_alpha=neftune_from_args(
                                   tc.hf_training_args_overrides, hf_args_overrides))
         if sharding_to_mode(sharding) in ("zero2", "zero3") and model.mmpt_config.classifier:
             raise NotImplementedError(  # before partition_out releases the module's storage

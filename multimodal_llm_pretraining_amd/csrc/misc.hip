@@ -4,10 +4,12 @@
 // bf16 shadow write, grad-norm and casts.  All loads/stores are 8-16 B per lane
 // (cdna_hip_programming.md Guideline 13); reductions are fixed-shape two-stage
 // so every result is bitwise reproducible run to run.
+#include <float.h>
 #include <math.h>
 #include <string.h>
 
 #include "common.h"
+#include "philox.h"
 
 namespace mmpt {
 namespace {
@@ -464,6 +466,47 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(int rows, int h, const i
   } else {
     const float4* src = (const float4*)(table + ids[row] * (long)h);
     for (int i = lane; i < nv; i += 64) o[i] = src[i];
+  }
+}
+
+// NEFTune (K8; HF's neftune_post_forward_hook on the input embedding): the gather above with
+// U(-mag, mag) noise added to the text rows in the same pass — the float4 at quad
+// q = row * h/4 + i takes the four words of dropout_words(q, site, seed) (philox.h
+// embed_noise_add: two separately rounded fp32 operations per element).  Image rows receive
+// the features unchanged: HF's masked_scatter overwrites those rows after the hook.  One wave
+// per row as above: 16-B loads and stores, ten Philox rounds per float4, nothing stored.
+__global__ __launch_bounds__(256) void embed_noise_fwd_kernel(int rows, int h, const int64_t* ids,
+                                                              const float* table,
+                                                              const int32_t* imap, const bf16_t* img,
+                                                              float* out, float mag, uint64_t seed,
+                                                              uint64_t site) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int nv = h >> 2;
+  float4* o = (float4*)(out + (long)row * h);
+  const int im = imap ? imap[row] : -1;
+  if (im >= 0) {
+    const bf16_t* src = img + (long)im * h;
+    for (int i = lane; i < nv; i += 64) o[i] = ld4bf(src + i * 4);
+  } else {
+    const float4* src = (const float4*)(table + ids[row] * (long)h);
+    for (int i = lane; i < nv; i += 64) {
+      const float4 v = src[i];
+      const philox4 k = dropout_words((uint64_t)row * nv + i, site, seed);
+      o[i] = make_float4(embed_noise_add(v.x, k.w[0], mag), embed_noise_add(v.y, k.w[1], mag),
+                         embed_noise_add(v.z, k.w[2], mag), embed_noise_add(v.w, k.w[3], mag));
+    }
+  }
+}
+// The noise alone, out[e] = noise of logical element e for e < 4 * nq (what mmpt_dropout_mask
+// is to the masks): one Philox call and one 16-B store per thread, grid-stride.
+__global__ __launch_bounds__(256) void embed_noise_kernel(long nq, float* out, float mag,
+                                                          uint64_t seed, uint64_t site) {
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+    const philox4 k = dropout_words((uint64_t)q, site, seed);
+    ((float4*)out)[q] = make_float4(embed_noise_of(k.w[0], mag), embed_noise_of(k.w[1], mag),
+                                    embed_noise_of(k.w[2], mag), embed_noise_of(k.w[3], mag));
   }
 }
 // Image-token rows of the embedding gradient: dimg[imap[row]] = bf16(dout[row]) (the
@@ -1150,6 +1193,37 @@ extern "C" int mmpt_embed_fwd(int64_t rows, int64_t h, const int64_t* ids, const
   embed_fwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(
       (int)rows, (int)h, ids, table, img_map, (const bf16_t*)img, out);
   return check_launch("embed_fwd");
+}
+// rows * h elements, h % 4 == 0, within what the noise addressing and the kernels' int rows cover
+#define MMPT_NOISE_ARGS(what)                                                                  \
+  MMPT_REQUIRE(rows > 0 && rows <= INT32_MAX && h > 0 && h % 4 == 0 && h <= INT32_MAX &&       \
+                   rows <= (INT64_MAX >> 2) / h,                                               \
+               what ": rows in [1, 2^31), h a positive multiple of 4 (rows %lld, h %lld)",    \
+               (long long)rows, (long long)h);                                                 \
+  MMPT_REQUIRE(mag >= 0.f && mag <= FLT_MAX, what ": mag must be finite and >= 0, got %g",    \
+               (double)mag)
+
+extern "C" int mmpt_embed_noise_fwd(int64_t rows, int64_t h, const int64_t* ids,
+                                    const float* table, const int32_t* img_map, const void* img,
+                                    float* out, float mag, uint64_t seed, uint64_t site,
+                                    void* stream) {
+  MMPT_NOISE_ARGS("embed_noise_fwd");
+  MMPT_REQUIRE(ids && table && out, "embed_noise_fwd: null pointer");
+  MMPT_REQUIRE(img_map == nullptr || img != nullptr, "embed_noise_fwd: img_map needs img");
+  MMPT_REQUIRE((((uintptr_t)table | (uintptr_t)out) & 15) == 0 && ((uintptr_t)img & 7) == 0,
+               "embed_noise_fwd: table / out must be 16-B aligned, img 8-B");
+  embed_noise_fwd_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(
+      (int)rows, (int)h, ids, table, img_map, (const bf16_t*)img, out, mag, seed, site);
+  return check_launch("embed_noise_fwd");
+}
+extern "C" int mmpt_embed_noise(int64_t rows, int64_t h, float mag, uint64_t seed, uint64_t site,
+                                float* out, void* stream) {
+  MMPT_NOISE_ARGS("embed_noise");
+  MMPT_REQUIRE(out && ((uintptr_t)out & 15) == 0, "embed_noise: out must be non-null, 16-B aligned");
+  const int64_t nq = rows * h / 4, g = (nq + 255) / 256, cap = (int64_t)cu_slots(nullptr) * 8;
+  embed_noise_kernel<<<(unsigned)(g > cap ? cap : g), 256, 0, (hipStream_t)stream>>>(
+      nq, out, mag, seed, site);
+  return check_launch("embed_noise");
 }
 extern "C" int mmpt_embed_bwd(int64_t rows, int64_t h, int64_t nseg, const int32_t* seg_id,
                               const int32_t* seg_off, const int32_t* perm, const int32_t* img_map,

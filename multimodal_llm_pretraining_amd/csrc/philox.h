@@ -1,7 +1,8 @@
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel Random Numbers: As Easy as 1, 2, 3",
 // SC'11; the Random123 constants), host and device: the counter-based generator behind the
 // hidden-dropout kernels (dropout.hip) and the attention-probability dropout of the
-// flash-attention kernels (attention.hip; the addressing further down).  A stand-alone header (no HIP include) so that a plain
+// flash-attention kernels (attention.hip; the addressing further down), and the embedding noise
+// of the gather kernels (misc.hip, postln.hip).  A stand-alone header (no HIP include) so that a plain
 // C++ program can check it against the published known answers.
 //
 // The dropout addressing (include/mmpt.h "K16"): logical element e = row*h + col of a
@@ -53,6 +54,48 @@ MMPT_PHILOX_HD philox4 dropout_words(uint64_t q, uint64_t site, uint64_t seed) {
 inline uint32_t dropout_threshold(double p) { return (uint32_t)(uint64_t)(p * 4294967296.0); }
 // 1 / (1 - p) rounded once to fp32: the factor kept elements are multiplied by.
 inline float dropout_scale(double p) { return (float)(1.0 / (1.0 - p)); }
+
+// ---- embedding noise (NEFTune; include/mmpt.h "K8") ----
+// Logical element e = row*h + col of noise site `site` takes word e % 4 of
+// dropout_words(e / 4, site, seed) (the hidden-dropout addressing) and adds
+//   noise = fmul_rn(s, mag),   s = (float)(2k + 1) * 2^-23 - 1,   k = word >> 9 (23 bits)
+// to its value: out = fadd_rn(value, noise), two separately rounded fp32 operations (never one
+// fma, so a numpy float32 restatement gives the same bits).  2k + 1 < 2^24 converts exactly,
+// the scaling by 2^-23 and the subtraction are exact, so s is an odd multiple of 2^-23 in
+// (-1, 1): symmetric about 0 and never 0.
+// Contraction is switched off where the two operations meet (hipcc honours the pragma under its
+// default -ffp-contract; HIP's __fmul_rn / __fadd_rn are plain operators without OCML's rounded
+// operations and would be fused).
+// s of one Philox word
+MMPT_PHILOX_HD float embed_noise_unit(uint32_t word) {
+  return (float)(int32_t)(2u * (word >> 9) + 1u) * 1.1920928955078125e-07f - 1.0f;
+}
+// noise = fmul_rn(s, mag) for one word
+MMPT_PHILOX_HD float embed_noise_of(uint32_t word, float mag) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+  return embed_noise_unit(word) * mag;
+#else
+  volatile float r = embed_noise_unit(word) * mag;  // rounded here, whatever the flags
+  return r;
+#endif
+}
+// value + noise for one word
+MMPT_PHILOX_HD float embed_noise_add(float value, uint32_t word, float mag) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float n = embed_noise_of(word, mag);
+  return value + n;
+}
+// The noise of logical element e alone (the tests' and mmpt_embed_noise's view).
+MMPT_PHILOX_HD float embed_noise_at(uint64_t e, uint64_t site, uint64_t seed, float mag) {
+  return embed_noise_of(dropout_words(e >> 2, site, seed).w[e & 3], mag);
+}
+// Host side: mag = alpha / sqrt(seq_in * hidden) in double, rounded once to fp32.
+inline float embed_noise_mag(double alpha, int64_t seq_in, int64_t hidden) {
+  return (float)(alpha / __builtin_sqrt((double)seq_in * (double)hidden));
+}
 
 // ---- attention-probability dropout (include/mmpt.h "K19") ----
 // The keep bit of probability (batch b, query head h, query position q, key position k) — positions

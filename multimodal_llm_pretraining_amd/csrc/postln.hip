@@ -15,6 +15,8 @@
 // kernel sums in block order.  No atomics: every result is bitwise reproducible.  The dropout
 // masks follow K16's element numbering (philox.h): the float4 at quad q = row * h/4 + i takes the
 // four words of dropout_words(q, site, seed).
+#include <float.h>
+
 #include "common.h"
 #include "philox.h"
 
@@ -23,7 +25,10 @@ namespace {
 
 constexpr int PL_WAVES = 4;
 constexpr int PL_BLOCKS = 1024;
-enum { PL_ADD = 0, PL_EMB = 1, PL_MLM = 2, PL_LN16 = 3 };  // LN16: MLM's backward without the dGELU
+enum { PL_ADD = 0, PL_EMB = 1, PL_MLM = 2, PL_LN16 = 3, PL_EMBN = 4 };  // LN16: MLM's backward without the dGELU
+// EMBN: EMB with NEFTune noise on the gathered word row (a mode of its own, so that EMB's
+// instantiations are the code they were)
+constexpr bool pl_emb(int mode) { return mode == PL_EMB || mode == PL_EMBN; }
 
 __device__ __forceinline__ float4 ld_bf16x4(const bf16_t* p) {
   const uint2 u = *(const uint2*)p;
@@ -76,6 +81,9 @@ struct PlArgs {
   uint32_t thr;
   float scale;
   uint64_t seed, site;
+  // EMBN: the embedding noise (philox.h embed_noise_add)
+  float nmag;
+  uint64_t nseed, nsite;
 };
 
 // Hands the compiler four plain registers: the row arithmetic below is then laid out as for a
@@ -92,6 +100,13 @@ __device__ __forceinline__ float4 emb_sum(const float4 t, const float4 ty, const
   return make_float4((t.x + ty.x) + ps.x, (t.y + ty.y) + ps.y, (t.z + ty.z) + ps.z,
                      (t.w + ty.w) + ps.w);
 }
+// EMBN: e = ((word[id] + noise) + type[0]) + pos[p] — HF's neftune hook sits on word_embeddings.
+// The forward and the backward both gather through this, so they draw the same noise.
+__device__ __forceinline__ float4 emb_noisy(float4 t, const PlArgs& a, int row, int nv, int i) {
+  const philox4 k = dropout_words((uint64_t)row * nv + i, a.nsite, a.nseed);
+  return make_float4(embed_noise_add(t.x, k.w[0], a.nmag), embed_noise_add(t.y, k.w[1], a.nmag),
+                     embed_noise_add(t.z, k.w[2], a.nmag), embed_noise_add(t.w, k.w[3], a.nmag));
+}
 
 template <int MODE, int MAXJ>
 __global__ __launch_bounds__(256) void postln_fwd_kernel(const PlArgs a) {
@@ -100,7 +115,7 @@ __global__ __launch_bounds__(256) void postln_fwd_kernel(const PlArgs a) {
   if (row >= a.rows) return;
   const int h = a.h, nv = h >> 2;
   const float4 *wr = nullptr, *pr = nullptr;
-  if (MODE == PL_EMB) {
+  if (pl_emb(MODE)) {
     wr = (const float4*)(a.word + clampl(a.ids[row], a.vocab) * h);
     pr = (const float4*)(a.ptab + clampl(a.pos[row], a.max_pos) * h);
   }
@@ -125,6 +140,8 @@ __global__ __launch_bounds__(256) void postln_fwd_kernel(const PlArgs a) {
         ((float4*)(a.s + (long)row * h))[i] = v[j];
       } else if (MODE == PL_EMB) {
         v[j] = emb_sum(wr[i], ((const float4*)a.type0)[i], pr[i]);
+      } else if (MODE == PL_EMBN) {
+        v[j] = emb_sum(emb_noisy(wr[i], a, row, nv, i), ((const float4*)a.type0)[i], pr[i]);
       } else {
         v[j] = ld_bf16x4(a.x16 + (long)row * a.ld_x16 + i * 4);
       }
@@ -154,7 +171,7 @@ __global__ __launch_bounds__(256) void postln_fwd_kernel(const PlArgs a) {
     const float4 g = ((const float4*)a.w)[i], bb = ((const float4*)a.b)[i];
     float4 y = make_float4((v[j].x - mean) * rstd * g.x + bb.x, (v[j].y - mean) * rstd * g.y + bb.y,
                            (v[j].z - mean) * rstd * g.z + bb.z, (v[j].w - mean) * rstd * g.w + bb.w);
-    if (MODE == PL_EMB && a.thr != 0) {  // h0 = dropout(y), fp32 (mmpt_dropout_f32's arithmetic)
+    if (pl_emb(MODE) && a.thr != 0) {  // h0 = dropout(y), fp32 (mmpt_dropout_f32's arithmetic)
       const philox4 k = dropout_words((uint64_t)row * nv + i, a.site, a.seed);
       y.x = k.w[0] >= a.thr ? y.x * a.scale : 0.f;
       y.y = k.w[1] >= a.thr ? y.y * a.scale : 0.f;
@@ -183,7 +200,7 @@ __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
   for (int row = blockIdx.x; row < a.rows; row += gridDim.x, par ^= 1) {
     const float mu = a.mean_in[row], rs = a.rstd_in[row];
     const float4 *wr = nullptr, *pr = nullptr;
-    if (MODE == PL_EMB) {
+    if (pl_emb(MODE)) {
       wr = (const float4*)(a.word + clampl(a.ids[row], a.vocab) * h);
       pr = (const float4*)(a.ptab + clampl(a.pos[row], a.max_pos) * h);
     }
@@ -206,8 +223,9 @@ __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
         } else {
           d1 = ld_bf16x4(a.dy16 + (long)row * a.ld_dy16 + i * 4);
         }
-      } else if (MODE == PL_EMB) {
-        xv = emb_sum(wr[i], ((const float4*)a.type0)[i], pr[i]);
+      } else if (pl_emb(MODE)) {
+        const float4 t = MODE == PL_EMBN ? emb_noisy(wr[i], a, row, nv, i) : wr[i];
+        xv = emb_sum(t, ((const float4*)a.type0)[i], pr[i]);
         d1 = ((const float4*)(a.dy32 + (long)row * h))[i];
         if (a.dy16 != nullptr) {  // + the bf16 input gradient of the GEMM that read bf16(h0)
           const float4 e = ld_bf16x4(a.dy16 + (long)row * a.ld_dy16 + i * 4);
@@ -252,7 +270,7 @@ __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
       o.z += rs * (g1[j].z - xh[j].z * c1a - c1b);
       o.w += rs * (g1[j].w - xh[j].w * c1a - c1b);
       if (MODE != PL_MLM && MODE != PL_LN16) ((float4*)(a.o32 + (long)row * h))[i] = o;
-      if (MODE == PL_EMB) {  // dtype[0] = Σ_rows de in fp32: these gradients are outside autocast
+      if (pl_emb(MODE)) {  // dtype[0] = Σ_rows de in fp32: these gradients are outside autocast
         aq[j].x += o.x; aq[j].y += o.y; aq[j].z += o.z; aq[j].w += o.w;
         continue;
       }
@@ -423,12 +441,19 @@ extern "C" int mmpt_add_layernorm_bwd(int64_t rows, int64_t h, const float* s, c
   MMPT_REQUIRE(al16(word) && al16(pos_table) && al16(type_row) && al16(w),                      \
                what ": pointers must be 16-byte aligned")
 
-extern "C" int mmpt_roberta_embed_fwd(int64_t rows, int64_t h, float eps, const int64_t* ids,
-                                      const int64_t* pos, const float* word, int64_t vocab,
-                                      const float* pos_table, int64_t max_pos,
-                                      const float* type_row, const float* w, const float* b,
-                                      float* h32, void* h16, float* mean, float* rstd, double p,
-                                      uint64_t seed, uint64_t site, void* stream) {
+// mag finite and >= 0 (a NaN fails both comparisons)
+#define MMPT_PL_MAG(what) \
+  MMPT_REQUIRE(mag >= 0.f && mag <= FLT_MAX, what ": mag must be finite and >= 0, got %g", (double)mag)
+
+// MODE = PL_EMB: mmpt_roberta_embed_fwd (mag, noise_site unused); PL_EMBN: the noise entry
+template <int MODE>
+static int roberta_embed_fwd_impl(int64_t rows, int64_t h, float eps, const int64_t* ids,
+                                  const int64_t* pos, const float* word, int64_t vocab,
+                                  const float* pos_table, int64_t max_pos, const float* type_row,
+                                  const float* w, const float* b, float* h32, void* h16,
+                                  float* mean, float* rstd, double p, uint64_t seed, uint64_t site,
+                                  float mag, uint64_t noise_seed, uint64_t noise_site,
+                                  void* stream) {
   MMPT_PL_SHAPE("roberta_embed_fwd");
   MMPT_PL_P("roberta_embed_fwd");
   MMPT_PL_EMB_ARGS("roberta_embed_fwd");
@@ -441,20 +466,48 @@ extern "C" int mmpt_roberta_embed_fwd(int64_t rows, int64_t h, float eps, const 
   a.vocab = (int)vocab; a.max_pos = (int)max_pos;
   a.o32 = h32; a.o16 = (bf16_t*)h16; a.ld_o16 = h; a.mean = mean; a.rstd = rstd;
   a.thr = dropout_threshold(p); a.scale = dropout_scale(p); a.seed = seed; a.site = site;
-  return launch_fwd<PL_EMB>(a, (hipStream_t)stream, "roberta_embed_fwd");
+  a.nmag = mag; a.nseed = noise_seed; a.nsite = noise_site;
+  return launch_fwd<MODE>(a, (hipStream_t)stream, "roberta_embed_fwd");
+}
+
+extern "C" int mmpt_roberta_embed_fwd(int64_t rows, int64_t h, float eps, const int64_t* ids,
+                                      const int64_t* pos, const float* word, int64_t vocab,
+                                      const float* pos_table, int64_t max_pos,
+                                      const float* type_row, const float* w, const float* b,
+                                      float* h32, void* h16, float* mean, float* rstd, double p,
+                                      uint64_t seed, uint64_t site, void* stream) {
+  return roberta_embed_fwd_impl<PL_EMB>(rows, h, eps, ids, pos, word, vocab, pos_table, max_pos,
+                                        type_row, w, b, h32, h16, mean, rstd, p, seed, site, 0.f,
+                                        0, 0, stream);
+}
+
+extern "C" int mmpt_roberta_embed_noise_fwd(int64_t rows, int64_t h, float eps, const int64_t* ids,
+                                            const int64_t* pos, const float* word, int64_t vocab,
+                                            const float* pos_table, int64_t max_pos,
+                                            const float* type_row, const float* w, const float* b,
+                                            float* h32, void* h16, float* mean, float* rstd,
+                                            double p, uint64_t seed, uint64_t site, float mag,
+                                            uint64_t noise_seed, uint64_t noise_site,
+                                            void* stream) {
+  MMPT_PL_MAG("roberta_embed_noise_fwd");
+  return roberta_embed_fwd_impl<PL_EMBN>(rows, h, eps, ids, pos, word, vocab, pos_table, max_pos,
+                                         type_row, w, b, h32, h16, mean, rstd, p, seed, site, mag,
+                                         noise_seed, noise_site, stream);
 }
 
 extern "C" int64_t mmpt_roberta_embed_bwd_workspace_bytes(int64_t rows, int64_t h) {
   return mmpt_add_layernorm_bwd_workspace_bytes(rows, h);
 }
 
-extern "C" int mmpt_roberta_embed_bwd(int64_t rows, int64_t h, const int64_t* ids,
-                                      const int64_t* pos, const float* word, int64_t vocab,
-                                      const float* pos_table, int64_t max_pos,
-                                      const float* type_row, const float* mean, const float* rstd,
-                                      const float* w, const float* dh, const void* dhb,
-                                      float* de, float* dw, float* db, float* dtype, double p, uint64_t seed,
-                                      uint64_t site, void* workspace, void* stream) {
+template <int MODE>
+static int roberta_embed_bwd_impl(int64_t rows, int64_t h, const int64_t* ids, const int64_t* pos,
+                                  const float* word, int64_t vocab, const float* pos_table,
+                                  int64_t max_pos, const float* type_row, const float* mean,
+                                  const float* rstd, const float* w, const float* dh,
+                                  const void* dhb, float* de, float* dw, float* db, float* dtype,
+                                  double p, uint64_t seed, uint64_t site, float mag,
+                                  uint64_t noise_seed, uint64_t noise_site, void* workspace,
+                                  void* stream) {
   MMPT_PL_SHAPE("roberta_embed_bwd");
   MMPT_PL_P("roberta_embed_bwd");
   MMPT_PL_EMB_ARGS("roberta_embed_bwd");
@@ -467,7 +520,38 @@ extern "C" int mmpt_roberta_embed_bwd(int64_t rows, int64_t h, const int64_t* id
   a.vocab = (int)vocab; a.max_pos = (int)max_pos;
   a.dy32 = dh; a.dy16 = (const bf16_t*)dhb; a.ld_dy16 = h; a.o32 = de; a.partials = (float*)workspace; a.want_q2 = dtype != nullptr;
   a.thr = dropout_threshold(p); a.scale = dropout_scale(p); a.seed = seed; a.site = site;
-  return launch_bwd<PL_EMB>(a, dw, db, dtype, nullptr, 0, (hipStream_t)stream, "roberta_embed_bwd");
+  a.nmag = mag; a.nseed = noise_seed; a.nsite = noise_site;
+  return launch_bwd<MODE>(a, dw, db, dtype, nullptr, 0, (hipStream_t)stream, "roberta_embed_bwd");
+}
+
+extern "C" int mmpt_roberta_embed_bwd(int64_t rows, int64_t h, const int64_t* ids,
+                                      const int64_t* pos, const float* word, int64_t vocab,
+                                      const float* pos_table, int64_t max_pos,
+                                      const float* type_row, const float* mean, const float* rstd,
+                                      const float* w, const float* dh, const void* dhb,
+                                      float* de, float* dw, float* db, float* dtype, double p, uint64_t seed,
+                                      uint64_t site, void* workspace, void* stream) {
+  return roberta_embed_bwd_impl<PL_EMB>(rows, h, ids, pos, word, vocab, pos_table, max_pos,
+                                        type_row, mean, rstd, w, dh, dhb, de, dw, db, dtype, p,
+                                        seed, site, 0.f, 0, 0, workspace, stream);
+}
+
+// The backward of mmpt_roberta_embed_noise_fwd: it gathers e again and so draws the forward's
+// noise again (same mag, noise_seed and noise_site); nothing random was stored.
+extern "C" int mmpt_roberta_embed_noise_bwd(int64_t rows, int64_t h, const int64_t* ids,
+                                            const int64_t* pos, const float* word, int64_t vocab,
+                                            const float* pos_table, int64_t max_pos,
+                                            const float* type_row, const float* mean,
+                                            const float* rstd, const float* w, const float* dh,
+                                            const void* dhb, float* de, float* dw, float* db,
+                                            float* dtype, double p, uint64_t seed, uint64_t site,
+                                            float mag, uint64_t noise_seed,
+                                            uint64_t noise_site, void* workspace, void* stream) {
+  MMPT_PL_MAG("roberta_embed_noise_bwd");
+  return roberta_embed_bwd_impl<PL_EMBN>(rows, h, ids, pos, word, vocab, pos_table, max_pos,
+                                         type_row, mean, rstd, w, dh, dhb, de, dw, db, dtype, p,
+                                         seed, site, mag, noise_seed, noise_site, workspace,
+                                         stream);
 }
 
 extern "C" int mmpt_mlm_ln_fwd(int64_t rows, int64_t h, float eps, const void* g, int64_t ld_g,

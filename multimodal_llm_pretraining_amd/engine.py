@@ -104,7 +104,8 @@ def sort_segments(ids: np.ndarray, rows: np.ndarray):
 # bits.  unit: 0 = the text embedding, 1 + i = text layer i, VISION_UNIT = the ViT embedding,
 # VISION_UNIT + 1 + i = ViT layer i (so at most 2047 layers a side); k: the site inside the
 # unit (a layer: 0 = after the attention output projection, 1 = after the MLP, 2 = the
-# attention probabilities — the site of the mmpt_attention_drop_* calls, which share the seed).
+# attention probabilities — the site of the mmpt_attention_drop_* calls, which share the seed;
+# unit 0 also has k = 4 = the NEFTune noise on the token embedding, Engine.neftune_alpha).
 # ConvNeXt: VISION_UNIT + 1 + j = block j counted over all stages, k = 3 = its drop-path bits
 # (element b = sample b; the blocks have no other site).
 SITE_STEPS, SITE_RANKS, SITE_UNITS, SITE_KS = 1 << 32, 1 << 16, 1 << 12, 1 << 4
@@ -189,6 +190,9 @@ class Batch:
         if input_ids is None:
             raise ValueError("a language model needs input_ids")
         self.B, self.S = input_ids.shape
+        # the width of input_ids as the batch arrived (padded / flattened / with the image
+        # slots): NEFTune's magnitude is alpha / sqrt(S_in * hidden), HF's output.size(1)
+        self.S_in = self.S
         cfg.text.check_seq(self.S)
         self.pos_ids, self.pos_segments = None, ()
         if cfg.multimodal and pixel_values is None:
@@ -530,6 +534,13 @@ class Engine:
         # label smoothing of the loss (TrainingArguments.label_smoothing_factor, HF's
         # LabelSmoother): every cross entropy below, training and forward-only, takes it
         self.label_smoothing = 0.0
+        # NEFTune (TrainingArguments.neftune_noise_alpha; HF's neftune_post_forward_hook on the
+        # input embedding): None = off, else U(-m, m) noise on the token-embedding rows with
+        # m = alpha / sqrt(Batch.S_in * hidden), drawn inside the gather kernels from
+        # (dropout_seed, dropout_site(micro-step, rank, unit 0, k 4)) and never stored.  It
+        # follows the hidden-dropout switch: on while dropout_enabled, off in eval
+        self.neftune_alpha: float | None = None
+        self._noise = None  # the K.EmbedNoise of the micro-step in flight
         # ZeRO-3 parameter residency (zero3.Zero3Residency): gathers a unit's weights
         # before use and reduce-scatters its gradients after its backward
         self.units = None
@@ -824,10 +835,10 @@ class Engine:
     def _site(self, unit: int, k: int) -> int:
         return dropout_site(self._dstep, self.rank, unit, k)
 
-    def _drop_begin(self, need_grad: bool) -> None:
-        """Fix the micro-step's dropout state (probabilities, mask counter) for the forward, its
-        backward and any recompute.  A forward without gradients previews the next step's masks
-        and leaves the counter alone."""
+    def _drop_begin(self, need_grad: bool, batch: Batch | None = None) -> None:
+        """Fix the micro-step's dropout state (probabilities, mask counter, and with `batch` the
+        embedding noise's magnitude and site) for the forward, its backward and any recompute.  A
+        forward without gradients previews the next step's masks and leaves the counter alone."""
         on = self.dropout_enabled
         self._pt = self.cfg.text.hidden_dropout if on and self.cfg.text is not None else 0.0
         self._pv = self.cfg.vision.hidden_dropout if on and self.cfg.multimodal and \
@@ -841,8 +852,13 @@ class Engine:
         self._pdp = cn.drop_path_rates() if on and need_grad and cn is not None and \
             cn.drop_path_rate > 0 else None
         self._kept = {}
+        self._noise = None
+        if on and batch is not None and self.neftune_alpha:
+            self._noise = K.EmbedNoise(
+                K.embed_noise_mag(self.neftune_alpha, batch.S_in, self.cfg.text.hidden),
+                self.dropout_seed, self._site(0, 4))
         if need_grad and (max(self._pt, self._pv, self._pat, self._pav) > 0 or
-                          self._pdp is not None):
+                          self._pdp is not None or self._noise is not None):
             self.dropout_step += 1
 
     def _drop_grad(self, d, p, unit, k, bias, out=None):
@@ -1655,13 +1671,14 @@ class Engine:
         region = getattr(self.units, "region", None)
         if region is not None:
             region()
-        self._drop_begin(need_grad)
+        self._drop_begin(need_grad, batch)
         h32, h16 = self._e(T, h, dtype=F32), self._e(T, h)
         m0, r0 = self._e(T, dtype=F32), self._e(T, dtype=F32)
         K.roberta_embed_fwd(batch.ids, batch.pos_ids, self.s.p("text.embed"),
                             self.s.p("text.pos_embed"), self.s.p("text.type_embed")[0],
                             self.s.p("text.embed_ln.weight"), self.s.p("text.embed_ln.bias"), t.eps,
-                            h32, h16, m0, r0, self._pt, self.dropout_seed, self._site(0, 0))
+                            h32, h16, m0, r0, self._pt, self.dropout_seed, self._site(0, 0),
+                            noise=self._noise)
         x = (h32, h16)
         for i in range(t.layers):
             self._unit_fwd(f"text.layers.{i}")
@@ -1727,7 +1744,7 @@ class Engine:
                             self.s.p("text.embed_ln.weight"), d32, d32, dhb=dyb,
                             dw=g("text.embed_ln.weight"), db=g("text.embed_ln.bias"),
                             dtype=g("text.type_embed")[0], p=self._pt, seed=self.dropout_seed,
-                            site=self._site(0, 0))
+                            site=self._site(0, 0), noise=self._noise)
         if self._side is not None:  # the tied decoder's weight gradient also lands in text.embed
             torch.cuda.current_stream(self.dev).wait_stream(self._side)
         K.embed_bwd(batch.segments, d32, g("text.embed"))
@@ -1834,11 +1851,11 @@ class Engine:
         region = getattr(self.units, "region", None)
         if region is not None:
             region()
-        self._drop_begin(need_grad)
+        self._drop_begin(need_grad, batch)
         self._scan_keep = need_grad
         h = self._e(T, t.hidden, dtype=F32)
         self._f32_fwd("text.embed")
-        K.embed_fwd(batch.ids, self.s.p("text.embed"), h, None, None)
+        K.embed_fwd(batch.ids, self.s.p("text.embed"), h, None, None, noise=self._noise)
         for i in range(t.layers):
             self._unit_fwd(f"text.layers.{i}")
             h = self._mamba_layer_fwd(i, h, B, S)
@@ -1917,11 +1934,12 @@ class Engine:
             region()
         if S > self.cos.shape[0]:
             raise ValueError(f"sequence {S} longer than the rope table {self.cos.shape[0]}")
-        self._drop_begin(need_grad)
+        self._drop_begin(need_grad, batch)
         img = self._vision_fwd(batch.pixels, B) if cfg.multimodal else None
         h = self._e(T, t.hidden, dtype=F32)
         self._f32_fwd("text.embed")
-        K.embed_fwd(batch.ids, self.s.p("text.embed"), h, batch.img_map, img)
+        # (NEFTune noise on the text rows first, then the dropout: HF's hook sits on embed_in)
+        K.embed_fwd(batch.ids, self.s.p("text.embed"), h, batch.img_map, img, noise=self._noise)
         if self._pt > 0:  # GPTNeoX emb_dropout, after the image-token merge
             K.dropout_f32(h, h, self._pt, self.dropout_seed, self._site(0, 0))
         layer_fwd = self._llama_layer_fwd if t.llama else self._text_layer_fwd

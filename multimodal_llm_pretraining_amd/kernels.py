@@ -7,6 +7,10 @@ call into the hand-written HIP library; nothing falls back to ATen.
 
 from __future__ import annotations
 
+import math
+import struct
+from typing import NamedTuple
+
 import torch
 
 from . import _lib
@@ -591,10 +595,39 @@ def expand_rows(src, row_map, dst) -> None:
               src.data_ptr(), _ld(src), dst.data_ptr(), _ld(dst), _stream())
 
 
-def embed_fwd(ids, table, out, img_map=None, img=None) -> None:
+class EmbedNoise(NamedTuple):
+    """NEFTune noise of one micro-step (include/mmpt.h K8): U(-mag, mag) drawn per element from
+    (seed, site); mag = embed_noise_mag(alpha, S_in, hidden)."""
+    mag: float
+    seed: int
+    site: int
+
+
+def embed_noise_mag(alpha: float, seq_in: int, hidden: int) -> float:
+    """alpha / sqrt(S_in * hidden) in double, rounded once to fp32 (returned as a Python float
+    that holds the fp32 value)."""
+    return struct.unpack("f", struct.pack("f", float(alpha) / math.sqrt(float(seq_in) * hidden)))[0]
+
+
+def embed_fwd(ids, table, out, img_map=None, img=None, noise: EmbedNoise | None = None) -> None:
+    """out[r] = table[ids[r]], or the image feature row where img_map[r] >= 0; with `noise` the
+    text rows get the noise added in the same pass (mmpt_embed_noise_fwd)."""
     rows, h = out.shape
-    _lib.call("mmpt_embed_fwd", rows, h, ids.data_ptr(), table.data_ptr(), _p(img_map), _p(img),
+    if noise is None:
+        _lib.call("mmpt_embed_fwd", rows, h, ids.data_ptr(), table.data_ptr(), _p(img_map),
+                  _p(img), out.data_ptr(), _stream())
+        return
+    _lib.call("mmpt_embed_noise_fwd", rows, h, ids.data_ptr(), table.data_ptr(), _p(img_map),
+              _p(img), out.data_ptr(), float(noise.mag), noise.seed & _U64, noise.site & _U64,
+              _stream())
+
+
+def embed_noise(rows: int, h: int, noise: EmbedNoise, device=None) -> torch.Tensor:
+    """fp32 [rows, h]: the noise of the logical elements of a site alone (test hook)."""
+    out = torch.empty(rows, h, dtype=torch.float32, device="cuda" if device is None else device)
+    _lib.call("mmpt_embed_noise", rows, h, float(noise.mag), noise.seed & _U64, noise.site & _U64,
               out.data_ptr(), _stream())
+    return out
 
 
 def embed_segments(ids, vocab: int, skip_id: int = -1):
@@ -829,23 +862,30 @@ def _embed_tables(ids, pos, word, pos_table, type_row, rows, h, name):
 
 
 def roberta_embed_fwd(ids, pos, word, pos_table, type_row, w, b, eps: float, h32, h16, mean, rstd,
-                      p: float = 0.0, seed: int = 0, site: int = 0) -> None:
-    """h32 = drop(LN((word[ids] + type_row) + pos_table[pos])), h16 = bf16(h32)."""
+                      p: float = 0.0, seed: int = 0, site: int = 0,
+                      noise: EmbedNoise | None = None) -> None:
+    """h32 = drop(LN((word[ids] + type_row) + pos_table[pos])), h16 = bf16(h32); with `noise` the
+    word row is word[ids] + noise (mmpt_roberta_embed_noise_fwd)."""
     rows, h = h32.shape
     _embed_tables(ids, pos, word, pos_table, type_row, rows, h, "roberta_embed_fwd")
     _dense(h32, torch.float32, (rows, h), "roberta_embed_fwd.h32")
     _dense(h16, torch.bfloat16, (rows, h), "roberta_embed_fwd.h16")
-    _lib.call("mmpt_roberta_embed_fwd", rows, h, float(eps), ids.data_ptr(), pos.data_ptr(),
-              word.data_ptr(), word.shape[0], pos_table.data_ptr(), pos_table.shape[0],
-              type_row.data_ptr(), w.data_ptr(), b.data_ptr(), h32.data_ptr(), h16.data_ptr(),
-              mean.data_ptr(), rstd.data_ptr(), float(p), seed & _U64, site & _U64, _stream())
+    args = (rows, h, float(eps), ids.data_ptr(), pos.data_ptr(),
+            word.data_ptr(), word.shape[0], pos_table.data_ptr(), pos_table.shape[0],
+            type_row.data_ptr(), w.data_ptr(), b.data_ptr(), h32.data_ptr(), h16.data_ptr(),
+            mean.data_ptr(), rstd.data_ptr(), float(p), seed & _U64, site & _U64)
+    if noise is None:
+        _lib.call("mmpt_roberta_embed_fwd", *args, _stream())
+    else:
+        _lib.call("mmpt_roberta_embed_noise_fwd", *args, float(noise.mag), noise.seed & _U64,
+                  noise.site & _U64, _stream())
 
 
 def roberta_embed_bwd(ids, pos, word, pos_table, type_row, mean, rstd, w, dh, de, dhb=None,
                       dw=None, db=None, dtype=None, p: float = 0.0, seed: int = 0,
-                      site: int = 0) -> None:
+                      site: int = 0, noise: EmbedNoise | None = None) -> None:
     """de = LN'(drop(dh + f32(dhb))) over the re-gathered embedding sum (de may be dh); dw / db /
-    dtype +=."""
+    dtype +=.  `noise`: the forward's, drawn again with the gather."""
     rows, h = dh.shape
     _embed_tables(ids, pos, word, pos_table, type_row, rows, h, "roberta_embed_bwd")
     _dense(dh, torch.float32, (rows, h), "roberta_embed_bwd.dh")
@@ -853,11 +893,15 @@ def roberta_embed_bwd(ids, pos, word, pos_table, type_row, mean, rstd, w, dh, de
     if dhb is not None:
         _dense(dhb, torch.bfloat16, (rows, h), "roberta_embed_bwd.dhb")
     ws = workspace(_lib.query("mmpt_roberta_embed_bwd_workspace_bytes", rows, h), slot=2)
-    _lib.call("mmpt_roberta_embed_bwd", rows, h, ids.data_ptr(), pos.data_ptr(), word.data_ptr(),
-              word.shape[0], pos_table.data_ptr(), pos_table.shape[0], type_row.data_ptr(),
-              mean.data_ptr(), rstd.data_ptr(), w.data_ptr(), dh.data_ptr(), _p(dhb), de.data_ptr(),
-              _p(dw), _p(db), _p(dtype), float(p), seed & _U64, site & _U64, ws.data_ptr(),
-              _stream())
+    args = (rows, h, ids.data_ptr(), pos.data_ptr(), word.data_ptr(),
+            word.shape[0], pos_table.data_ptr(), pos_table.shape[0], type_row.data_ptr(),
+            mean.data_ptr(), rstd.data_ptr(), w.data_ptr(), dh.data_ptr(), _p(dhb), de.data_ptr(),
+            _p(dw), _p(db), _p(dtype), float(p), seed & _U64, site & _U64)
+    if noise is None:
+        _lib.call("mmpt_roberta_embed_bwd", *args, ws.data_ptr(), _stream())
+    else:
+        _lib.call("mmpt_roberta_embed_noise_bwd", *args, float(noise.mag), noise.seed & _U64,
+                  noise.site & _U64, ws.data_ptr(), _stream())
 
 
 def mlm_ln_fwd(g, w, b, eps: float, n16, mean, rstd) -> None:

@@ -14,6 +14,7 @@ single-process step exactly.
 
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass
 
@@ -45,9 +46,13 @@ class StepConfig:
     # TrainingArguments.label_smoothing_factor: the loss is F.cross_entropy's with
     # label_smoothing (HF Trainer's LabelSmoother), in training and in forward-only steps
     label_smoothing: float = 0.0
+    # TrainingArguments.neftune_noise_alpha: U(-m, m) noise on the token embeddings in training
+    # mode, m = alpha / sqrt(seq_len * hidden) (HF Trainer's neftune hook); None or 0 = off
+    neftune_noise_alpha: float | None = None
 
     def __post_init__(self):
         self.label_smoothing = check_label_smoothing(self.label_smoothing)
+        self.neftune_noise_alpha = check_neftune_alpha(self.neftune_noise_alpha)
 
 
 def check_label_smoothing(value, name: str = "label_smoothing") -> float:
@@ -68,6 +73,28 @@ def label_smoothing_from_args(*args: dict) -> float:
                                  "label_smoothing_factor")
 
 
+def check_neftune_alpha(value, name: str = "neftune_noise_alpha") -> float | None:
+    """None (off) for None or 0, else the alpha as a float; ValueError unless it is finite and
+    > 0."""
+    if value is None:
+        return None
+    alpha = float(value)
+    if alpha == 0.0:
+        return None
+    if not 0.0 < alpha < math.inf:  # (NaN fails both comparisons)
+        raise ValueError(f"{name} must be None, 0 or a finite number > 0, got {value!r}")
+    return alpha
+
+
+def neftune_from_args(*args: dict) -> float | None:
+    """`neftune_noise_alpha` of TrainingArguments dicts merged left to right (a later dict wins,
+    as for label_smoothing_from_args); absent = None."""
+    merged: dict = {}
+    for a in args:
+        merged.update(a or {})
+    return check_neftune_alpha(merged.get("neftune_noise_alpha"))
+
+
 class ManualTrainer:
     def __init__(self, step_cfg: StepConfig, adam: AdamConfig, device: torch.device | str = "cuda",
                  model_cfg: C.ModelConfig | None = None, group=None,
@@ -81,6 +108,11 @@ class ManualTrainer:
         self.device = torch.device(device)
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        if step_cfg.neftune_noise_alpha is not None and self.cfg.classifier:
+            raise NotImplementedError(
+                f"neftune_noise_alpha for the image classifier "
+                f"{C.preset_name(self.cfg) or step_cfg.model!r}: it has no token embedding to add "
+                "the noise to")
         mode = sharding_to_mode(step_cfg.sharding)
         if mode == "unsupported":
             raise NotImplementedError(f"sharding {step_cfg.sharding!r} not implemented yet")
@@ -139,6 +171,7 @@ class ManualTrainer:
         self.engine = engine if engine is not None else Engine(self.cfg, self.store)
         self.engine.checkpointing = step_cfg.activation_checkpointing
         self.engine.label_smoothing = step_cfg.label_smoothing
+        self.engine.neftune_alpha = step_cfg.neftune_noise_alpha
         if self.unit_mode:
             self.sync = Zero3Sync(self.store, self.engine.unit_order(), group,
                                   quant=step_cfg.sharding == "zero_3++")

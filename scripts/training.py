@@ -13,7 +13,9 @@ TrainingArguments keys honoured (everything the reference's JSON sets):
   lr_scheduler_kwargs.min_lr_rate, warmup_steps, gradient_checkpointing, bf16 (must be
   true: the step computes in bf16 autocast semantics), max_grad_norm, seed,
   label_smoothing_factor (default 0; HF Trainer's LabelSmoother: the cross-entropy kernels
-  smooth on the GPU, LabelSmoother itself on the CPU path), and the
+  smooth on the GPU, LabelSmoother itself on the CPU path), neftune_noise_alpha (default
+  off; HF Trainer's NEFTune hook: the embedding gather kernels add the noise on the GPU, a
+  forward hook on the input embedding on the CPU path), and the
   sharding given by `deepspeed.zero_optimization` (stage, offload_optimizer,
   offload_param) or `fsdp` ("shard_grad_op" / "full_shard" / "hybrid_shard[_zero2]"
   + "offload").  tf32 / torch_compile / fsdp_config are accepted and have no effect.
@@ -113,6 +115,20 @@ def smoothed_loss(model, model_config, batch: dict, factor: float, num_items: in
                                          num_items_in_batch=num_items)
 
 
+def neftune_hook(model, alpha: float):
+    """Trainer._activate_neftune: a forward hook on the input embedding that adds U(-m, m) noise
+    in training mode, m = alpha / sqrt(seq_len * hidden) (transformers/integrations/neftune.py)."""
+    import torch
+
+    def hook(module, args, output):
+        if module.training:
+            m = alpha / (output.size(1) * output.size(2)) ** 0.5
+            output = output + torch.zeros_like(output).uniform_(-m, m)
+        return output
+
+    return model.get_input_embeddings().register_forward_hook(hook)
+
+
 def train_cpu(output_dir: str, model_type: str, training_arguments: dict,
               max_steps: int | None = None, log_every: int = 1) -> list[dict]:
     """BASELINE C1: the naive eager model on the CPU, world size 1, fp32."""
@@ -120,10 +136,11 @@ def train_cpu(output_dir: str, model_type: str, training_arguments: dict,
 
     from multimodal_llm_pretraining_amd.models import get_model_class
     from multimodal_llm_pretraining_amd.optim import Schedule, min_lr_rate_of
-    from multimodal_llm_pretraining_amd.trainer import label_smoothing_from_args
+    from multimodal_llm_pretraining_amd.trainer import label_smoothing_from_args, neftune_from_args
 
     a = training_arguments
     smoothing = label_smoothing_from_args(a)
+    neftune = neftune_from_args(a)
     if int(os.environ.get("WORLD_SIZE", "1")) != 1:
         raise NotImplementedError("the CPU path runs at world size 1 (BASELINE C1)")
     mc = get_model_class(model_type)
@@ -132,6 +149,11 @@ def train_cpu(output_dir: str, model_type: str, training_arguments: dict,
     if a.get("gradient_checkpointing", False):
         model.gradient_checkpointing_enable()
     model.train()
+    if neftune is not None:
+        if mc.model_config.classifier:
+            raise NotImplementedError(f"neftune_noise_alpha for the image classifier "
+                                      f"{model_type!r}: it has no token embedding")
+        neftune_hook(model, neftune)
     kw = dict(mc.optimizer_kwargs)
     # HF's parameter groups apply TrainingArguments.weight_decay (default 0)
     kw["weight_decay"] = float(a.get("weight_decay", 0.0))
@@ -192,7 +214,8 @@ def train(output_dir: str, model_type: str, training_arguments: dict, max_steps:
     from multimodal_llm_pretraining_amd.models import get_model_class
     from multimodal_llm_pretraining_amd.optim import min_lr_rate_of
     from multimodal_llm_pretraining_amd.trainer import (ManualTrainer, StepConfig,
-                                                        label_smoothing_from_args)
+                                                        label_smoothing_from_args,
+                                                        neftune_from_args)
 
     a = training_arguments
     if not a.get("bf16", False) or a.get("fp16", False):
@@ -219,7 +242,8 @@ def train(output_dir: str, model_type: str, training_arguments: dict, max_steps:
                    num_warmup_steps=int(a.get("warmup_steps", 0)),
                    num_training_steps=int(a.get("max_steps", steps)),
                    min_lr_rate=min_lr_rate_of(sched_kw, adam.lr),
-                   label_smoothing=label_smoothing_from_args(a)),
+                   label_smoothing=label_smoothing_from_args(a),
+                   neftune_noise_alpha=neftune_from_args(a)),
         adam, device, model_cfg=mc.model_config)
     ds = mc.load_dummy_dataset()
     os.makedirs(output_dir, exist_ok=True)

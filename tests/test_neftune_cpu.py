@@ -1,0 +1,355 @@
+"""CPU-only tests of NEFTune (TrainingArguments.neftune_noise_alpha): the noise rule of
+csrc/philox.h against the numpy restatement (tests/neftune_ref.py), its distribution, the noise
+site, the argument path, the magnitude's sequence width and the C ABI.
+"""
+
+import itertools
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import neftune_ref as NR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PHILOX_H = os.path.join(ROOT, "multimodal_llm_pretraining_amd", "csrc", "philox.h")
+
+
+def f32_bits(x) -> int:
+    return int(np.asarray(x, dtype=np.float32).view(np.uint32))
+
+
+# ------------------------------------------------------------------ the header itself
+PROGRAM = r"""
+#include <cinttypes>
+#include <cstdio>
+#include <cstdlib>
+#include "philox.h"
+// stdin lines "e site seed mag_bits value_bits" (hex) -> "noise_bits sum_bits" (hex): the noise
+// of logical element e (embed_noise_at) and value + noise through embed_noise_add on the word
+// the addressing names; a line "m alpha seq hidden" (decimal) -> the bits of embed_noise_mag
+static float f_of(uint32_t b) { float f; __builtin_memcpy(&f, &b, 4); return f; }
+static uint32_t b_of(float f) { uint32_t b; __builtin_memcpy(&b, &f, 4); return b; }
+int main() {
+  char line[256];
+  while (fgets(line, sizeof line, stdin)) {
+    if (line[0] == 'm') {
+      double alpha; long long seq, hidden;
+      if (sscanf(line + 1, "%lf %lld %lld", &alpha, &seq, &hidden) != 3) return 2;
+      printf("%08x\n", b_of(mmpt::embed_noise_mag(alpha, seq, hidden)));
+      continue;
+    }
+    unsigned long long e, site, seed; unsigned mb, vb;
+    if (sscanf(line, "%llx %llx %llx %x %x", &e, &site, &seed, &mb, &vb) != 5) return 2;
+    const float mag = f_of(mb);
+    const mmpt::philox4 w = mmpt::dropout_words(e >> 2, site, seed);
+    printf("%08x %08x\n", b_of(mmpt::embed_noise_at(e, site, seed, mag)),
+           b_of(mmpt::embed_noise_add(f_of(vb), w.w[e & 3], mag)));
+  }
+  return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def noise_exe(tmp_path_factory):
+    d = tmp_path_factory.mktemp("neftune")
+    src, exe = str(d / "noise_check.cpp"), str(d / "noise_check")
+    with open(src, "w") as f:
+        f.write(PROGRAM)
+    subprocess.run(["g++", "-std=c++17", "-O2", "-g", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-I", os.path.dirname(PHILOX_H), src, "-o", exe],
+                   check=True)
+
+    def run(text):
+        r = subprocess.run([exe], input=text, capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        return [[int(x, 16) for x in ln.split()] for ln in r.stdout.splitlines()]
+
+    return run
+
+
+def test_header_noise_is_the_numpy_reference(noise_exe):
+    """A few thousand (e, site, seed, mag, value): e across multiple-of-4 boundaries and with
+    e / 4 >= 2^32; bitwise."""
+    rng = np.random.default_rng(5)
+    es = list(range(0, 13)) + [(1 << 34) - 2 + i for i in range(6)] + \
+        [(1 << 34) + 4 * 7 + i for i in range(5)] + [(1 << 40) + 3, (1 << 62) + 1] + \
+        [int(x) for x in rng.integers(0, 1 << 36, 40)]
+    assert any(e >> 2 >= 1 << 32 for e in es)
+    sites = [0, 4, (3 << 32) | (1 << 16) | 4, 0xABCDEF0123456784]
+    seeds = [0, 1234, (1 << 63) | 17]
+    mags = [np.float32(0.0), NR.mag_of(5, 130, 64), NR.mag_of(5, 707, 2048), np.float32(1.0),
+            np.float32(0.3)]
+    cases = [(e, st, sd, m, np.float32(v))
+             for (e, st, sd, m), v in zip(itertools.product(es, sites, seeds, mags),
+                                          rng.standard_normal(10 ** 5).astype(np.float32) * 0.05)]
+    assert len(cases) >= 3000
+    text = "".join(f"{e:x} {st:x} {sd:x} {f32_bits(m):x} {f32_bits(v):x}\n"
+                   for e, st, sd, m, v in cases)
+    got = noise_exe(text)
+    assert len(got) == len(cases)
+    for (st, sd, m), grp in itertools.groupby(zip(cases, got), key=lambda c: c[0][1:4]):
+        grp = list(grp)
+        e = np.array([c[0][0] for c in grp], dtype=np.uint64)
+        v = np.array([c[0][4] for c in grp], dtype=np.float32)
+        nz = NR.noise_at(e, st, sd, m)
+        want = np.stack([nz.view(np.uint32), NR.add(v, nz).view(np.uint32)], axis=1)
+        have = np.array([c[1] for c in grp], dtype=np.uint32)
+        assert (have == want).all(), (st, sd, m, e[(have != want).any(1)][:4])
+
+
+def test_header_mag_is_one_rounding_of_the_double(noise_exe):
+    shapes = [(5, 130, 64), (5, 707, 2048), ("5", 48, 64), (0.1, 1, 8), (15, 2049, 2560)]
+    got = noise_exe("".join(f"m {float(a)!r} {s} {h}\n" for a, s, h in shapes))
+    from multimodal_llm_pretraining_amd import kernels as K
+
+    for (a, s, h), (bits,) in zip(shapes, got):
+        assert bits == f32_bits(NR.mag_of(float(a), s, h)), (a, s, h)
+        assert f32_bits(K.embed_noise_mag(float(a), s, h)) == bits
+
+
+# ------------------------------------------------------------------ distribution
+def test_unit_distribution():
+    """s over n = 2^20 draws of site (step 3, rank 1, unit 0, k 4), seed 1234: inside (-1, 1),
+    never 0, mean within 6 / sqrt(3n) of 0 (var s = 1/3), variance within 6 standard errors of
+    1/3 (var s^2 = 4/45)."""
+    from multimodal_llm_pretraining_amd.engine import dropout_site
+
+    n = 1 << 20
+    s = NR.unit(NR.words(np.arange(n, dtype=np.uint64), dropout_site(3, 1, 0, 4), 1234))
+    assert s.dtype == np.float32
+    assert (np.abs(s) < 1).all() and (s != 0).all()
+    # odd multiples of 2^-23: s * 2^23 is an odd integer
+    k = (s.astype(np.float64) * 2.0 ** 23)
+    assert (k == np.round(k)).all() and (k.astype(np.int64) % 2 == 1).all()
+    s64 = s.astype(np.float64)
+    mean, var = s64.mean(), (s64 ** 2).mean()
+    print(f"mean {mean:.3e} (bound {6 / math.sqrt(3 * n):.3e}), var - 1/3 {var - 1 / 3:.3e} "
+          f"(bound {6 * math.sqrt(4 / 45 / n):.3e})")
+    assert abs(mean) <= 6 / math.sqrt(3 * n)
+    assert abs(var - 1 / 3) <= 6 * math.sqrt(4 / 45 / n)
+    # symmetric: word w and its complement give s and -s
+    w = np.array([0, 1 << 9, 0x12345600, 0xFFFFFFFF], dtype=np.uint32)
+    assert (NR.unit(w) == -NR.unit(~w)).all()
+    assert NR.unit(np.uint32(0)) == np.float32(2.0 ** -23 - 1)
+    assert NR.unit(np.uint32(0xFFFFFFFF)) == np.float32(1 - 2.0 ** -23)
+
+
+# ------------------------------------------------------------------ the site
+def test_noise_site_is_new():
+    """(unit 0, k 4) differs from every site the engine uses: units take k 0..2, ConvNeXt blocks
+    k 3."""
+    import inspect
+
+    from multimodal_llm_pretraining_amd import engine as E
+
+    used = {E.dropout_site(st, r, u, k) for st in (0, 1, 7) for r in (0, 3)
+            for u in list(range(0, 40)) + list(range(E.VISION_UNIT, E.VISION_UNIT + 40))
+            for k in (0, 1, 2, 3)}
+    for st in (0, 1, 7):
+        for r in (0, 3):
+            assert E.dropout_site(st, r, 0, 4) not in used
+    # and the engine's source names no other k = 4 site
+    src = inspect.getsource(E.Engine)
+    assert re.findall(r"_site\([^()]*,\s*4\)", src) == ["_site(0, 4)"]
+    assert 4 < E.SITE_KS
+
+
+# ------------------------------------------------------------------ arguments
+def test_check_and_from_args():
+    from multimodal_llm_pretraining_amd.trainer import check_neftune_alpha as chk
+    from multimodal_llm_pretraining_amd.trainer import neftune_from_args as f
+
+    assert chk(None) is None and chk(0) is None and chk(0.0) is None and chk("0") is None
+    assert chk(5) == 5.0 and chk("5") == 5.0 and isinstance(chk(5), float)
+    for bad in (-1, -0.5, float("nan"), float("inf"), "-3"):
+        with pytest.raises(ValueError, match="neftune_noise_alpha"):
+            chk(bad)
+    assert f() is None and f({}) is None and f({"weight_decay": 0.1}) is None
+    assert f({"neftune_noise_alpha": None}) is None and f({"neftune_noise_alpha": 0}) is None
+    assert f({"neftune_noise_alpha": 5}) == 5.0 and f({"neftune_noise_alpha": "5"}) == 5.0
+    assert f({"neftune_noise_alpha": 5}, {"neftune_noise_alpha": 10}) == 10.0
+    assert f({"neftune_noise_alpha": 5}, {}) == 5.0
+    assert f({"neftune_noise_alpha": 5}, {"neftune_noise_alpha": None}) is None
+    for bad in (-1, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="neftune_noise_alpha"):
+            f({"neftune_noise_alpha": 5}, {"neftune_noise_alpha": bad})
+
+
+def test_step_config_and_training_class_carry_it():
+    from multimodal_llm_pretraining_amd.train import TrainingClass
+    from multimodal_llm_pretraining_amd.trainer import StepConfig, neftune_from_args
+
+    assert StepConfig().neftune_noise_alpha is None
+    assert StepConfig(neftune_noise_alpha=0).neftune_noise_alpha is None
+    assert StepConfig(neftune_noise_alpha="5").neftune_noise_alpha == 5.0
+    for bad in (-1, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="neftune_noise_alpha"):
+            StepConfig(neftune_noise_alpha=bad)
+    kw = dict(num_training_steps=10, micro_batch_size=2, gradient_accumulation_steps=1)
+    tc = TrainingClass(**kw, hf_training_args_overrides={"neftune_noise_alpha": 5})
+    d = tc._to_huggingface_args_dict()
+    assert d["neftune_noise_alpha"] == 5
+    assert tc._to_huggingface_args_dict(weight_decay=0.1)["neftune_noise_alpha"] == 5
+    assert neftune_from_args(tc.hf_training_args_overrides, {}) == 5.0
+    assert TrainingClass(**kw)._to_huggingface_args_dict(
+        neftune_noise_alpha=3)["neftune_noise_alpha"] == 3
+
+
+@pytest.mark.parametrize("name", ["tiny-vit-cls", "tiny-convnext"])
+def test_image_classifiers_refuse_it(name):
+    from multimodal_llm_pretraining_amd.optim import AdamConfig
+    from multimodal_llm_pretraining_amd.trainer import ManualTrainer, StepConfig
+
+    with pytest.raises(NotImplementedError, match=name) as ei:
+        ManualTrainer(StepConfig(model=name, neftune_noise_alpha=5), AdamConfig(), "cpu")
+    assert "neftune_noise_alpha" in str(ei.value)
+
+
+def test_engine_default_and_wrappers():
+    import inspect
+
+    from multimodal_llm_pretraining_amd import kernels as K
+    from multimodal_llm_pretraining_amd.engine import Engine
+
+    for fn in (K.embed_fwd, K.roberta_embed_fwd, K.roberta_embed_bwd):
+        assert inspect.signature(fn).parameters["noise"].default is None
+    src = inspect.getsource(Engine)
+    assert src.count("noise=self._noise") == 4  # three forwards and the RoBERTa backward
+    assert "self.neftune_alpha: float | None = None" in src
+
+
+# ------------------------------------------------------------------ the magnitude's width
+def _cpu_engine(name):
+    from multimodal_llm_pretraining_amd import config as C
+    from multimodal_llm_pretraining_amd.engine import Engine
+    from multimodal_llm_pretraining_amd.params import ParamStore
+
+    cfg = C.get_config(name)
+    return cfg, Engine(cfg, ParamStore(C.param_shapes(cfg), "cpu"))
+
+
+def test_magnitude_uses_the_arriving_width():
+    """mag = alpha / sqrt(S_in * hidden) with S_in = input_ids.shape[1]: the padded width of a
+    padded batch, the flattened width of a packed row — never the valid or document lengths."""
+    from multimodal_llm_pretraining_amd.engine import Batch, dropout_site
+
+    g = torch.Generator().manual_seed(0)
+    # right-padded: 2 x 24, lengths 24 and 9
+    cfg, eng = _cpu_engine("tiny-lm")
+    ids = torch.randint(3, cfg.text.n_vocab, (2, 24), generator=g)
+    mask = torch.ones(2, 24, dtype=torch.int64)
+    mask[1, 9:] = 0
+    b = Batch(cfg, ids, ids.clone(), None, "cpu", attention_mask=mask)
+    assert (b.S_in, b.T, b.max_len) == (24, 33, 24)
+    eng.neftune_alpha, eng.dropout_seed = 5.0, 77
+    eng._drop_begin(True, b)
+    want = NR.mag_of(5, 24, cfg.text.hidden)
+    assert f32_bits(eng._noise.mag) == f32_bits(want)
+    assert f32_bits(eng._noise.mag) != f32_bits(NR.mag_of(5, 9, cfg.text.hidden))
+    assert eng._noise.seed == 77 and eng._noise.site == dropout_site(0, eng.rank, 0, 4)
+    assert eng.dropout_step == 1  # advanced although every dropout probability is 0
+    eng._drop_begin(False, b)  # a preview: the next step's site, the counter left alone
+    assert eng._noise.site == dropout_site(1, eng.rank, 0, 4) and eng.dropout_step == 1
+    eng.dropout_enabled = False
+    eng._drop_begin(True, b)
+    assert eng._noise is None and eng.dropout_step == 1
+    eng.dropout_enabled, eng.neftune_alpha = True, None
+    eng._drop_begin(True, b)
+    assert eng._noise is None and eng.dropout_step == 1
+    # packed: one row of 30 holding documents of 11, 12 and 7 tokens
+    cfg, eng = _cpu_engine("tiny-mamba")
+    ids = torch.randint(3, cfg.text.n_vocab, (1, 30), generator=g)
+    pos = torch.cat([torch.arange(11), torch.arange(12), torch.arange(7)])[None]
+    b = Batch(cfg, ids, ids.clone(), None, "cpu", position_ids=pos)
+    assert (b.S_in, b.lens, b.max_len) == (30, [11, 12, 7], 12)
+    eng.neftune_alpha = 5.0
+    eng._drop_begin(True, b)
+    assert f32_bits(eng._noise.mag) == f32_bits(NR.mag_of(5, 30, cfg.text.hidden))
+
+
+# ------------------------------------------------------------------ header / binding
+def test_header_and_binding_agree():
+    from multimodal_llm_pretraining_amd import _lib
+
+    src = open(os.path.join(ROOT, "include", "mmpt.h")).read()
+    assert re.search(r"#define MMPT_ABI_VERSION (\d+)", src).group(1) == "16"  # entries only added
+    assert _lib.ABI_VERSION == 16
+    ctypes_of = {"int64_t": "I64", "int": "I32", "float": "F32", "double": "F64", "uint64_t": "U64"}
+    sigs = {}
+    for name in ("mmpt_embed_fwd", "mmpt_embed_noise_fwd", "mmpt_embed_noise",
+                 "mmpt_roberta_embed_fwd", "mmpt_roberta_embed_noise_fwd",
+                 "mmpt_roberta_embed_bwd", "mmpt_roberta_embed_noise_bwd"):
+        m = re.search(r"\bint " + name + r"\s*\(([^)]*)\)\s*;", src)
+        assert m, name
+        args = [" ".join(a.split()) for a in m.group(1).split(",")]
+        types = ["P" if "*" in a else ctypes_of[a.rsplit(" ", 1)[0]] for a in args]
+        res, argtypes = _lib.SIGNATURES[name]
+        assert res is _lib.I32 and argtypes == [getattr(_lib, t) for t in types], (name, types)
+        sigs[name] = [a.rsplit(" ", 1)[1].lstrip("*") for a in args]
+    assert sigs["mmpt_embed_noise_fwd"] == sigs["mmpt_embed_fwd"][:-1] + \
+        ["mag", "seed", "site", "stream"]
+    assert sigs["mmpt_embed_noise"] == "rows h mag seed site out stream".split()
+    extra = ["mag", "noise_seed", "noise_site"]
+    assert sigs["mmpt_roberta_embed_noise_fwd"] == sigs["mmpt_roberta_embed_fwd"][:-1] + extra + \
+        ["stream"]
+    assert sigs["mmpt_roberta_embed_noise_bwd"] == sigs["mmpt_roberta_embed_bwd"][:-2] + extra + \
+        ["workspace", "stream"]
+    lib = _lib.load()
+    assert lib.mmpt_abi_version() == 16
+    for name in ("mmpt_embed_noise_fwd", "mmpt_embed_noise", "mmpt_roberta_embed_noise_fwd",
+                 "mmpt_roberta_embed_noise_bwd"):
+        assert hasattr(lib, name)
+
+
+# ------------------------------------------------------------------ the oracle hook
+def test_embedding_hook_adds_to_one_table_and_restores():
+    import torch.nn.functional as F
+
+    orig = F.embedding
+    word, other = torch.randn(10, 4), torch.randn(10, 4)
+    ids = torch.tensor([[1, 2, 3], [4, 5, 6]])
+    nz = np.arange(24, dtype=np.float32).reshape(6, 4)
+    with NR.embedding_hook(word, nz) as calls:
+        a = F.embedding(ids, word)
+        b = F.embedding(ids, other)
+    assert calls == [1] and F.embedding is orig
+    assert torch.equal(a, word[ids] + torch.from_numpy(nz).reshape(2, 3, 4))
+    assert torch.equal(b, other[ids])
+
+
+# ------------------------------------------------------------------ scripts/training.py, CPU path
+@pytest.mark.parametrize("name", ["tiny-lm", "tiny-roberta", "tiny-mamba"])
+def test_training_script_cpu_hook(name):
+    """neftune_hook on the plain transformers model: HF's hook — noise within
+    alpha / sqrt(seq_len * hidden) on the input embedding in training mode, none in eval."""
+    import importlib.util
+
+    from multimodal_llm_pretraining_amd import config as C
+    from multimodal_llm_pretraining_amd.models import build_hf_model
+
+    spec = importlib.util.spec_from_file_location("training_script",
+                                                  os.path.join(ROOT, "scripts", "training.py"))
+    script = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(script)
+    cfg = C.get_config(name)
+    torch.manual_seed(0)
+    model = build_hf_model(cfg).eval()
+    ids = torch.randint(3, cfg.text.n_vocab, (2, 12))
+    with torch.no_grad():
+        plain = model(input_ids=ids).logits
+        handle = script.neftune_hook(model, 5.0)
+        assert torch.equal(model(input_ids=ids).logits, plain)  # eval: no noise
+        model.train()
+        assert not torch.equal(model(input_ids=ids).logits, plain)
+        emb = model.get_input_embeddings()
+        d = (emb(ids) - torch.nn.functional.embedding(ids, emb.weight)).abs().max().item()
+        handle.remove()
+        assert torch.equal(emb(ids), torch.nn.functional.embedding(ids, emb.weight))
+    mag = 5.0 / math.sqrt(12 * cfg.text.hidden)
+    assert 0.5 * mag < d <= mag

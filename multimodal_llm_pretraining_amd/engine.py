@@ -34,12 +34,17 @@ GEMMs over those rows (_convnext_forward / _convnext_backward).
 A Mamba language model (TextConfig.arch "mamba": MambaForCausalLM,
 tf:models/mamba/modeling_mamba.py) has no attention: each block is an RMSNorm, five GEMMs, the
 causal conv and the selective scan of include/mmpt.h K22, with the arithmetic of the reference's
-fused path (_mamba_forward / _mamba_backward).
+fused path; around its blocks it is the causal-LM step (_causal_forward / _causal_backward).
+
+Every family's step runs in one frame: _begin (the prologue), the family's body, _loss (cross
+entropy + sum, and what a forward without gradients keeps: nothing); _begin_backward (the head's
+cache entry, dlogits scaled), the body, _finish.  Engine.__init__ picks the family once.
 """
 
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -121,6 +126,36 @@ def dropout_site(step: int, rank: int, unit: int, k: int) -> int:
         if not 0 <= v < n:
             raise ValueError(f"dropout_site: {name} {v} outside [0, {n})")
     return (step << 32) | (rank << 16) | (unit << 4) | k
+
+
+class AttnLayout(NamedTuple):
+    """Where the heads sit in a row of the fused qkv GEMM output, in elements (the layout arguments
+    of mmpt_attention_gqa_fwd): q head j at j * head_stride, its kv head at k_offset / v_offset +
+    (j // (heads / kv_heads)) * head_stride."""
+    heads: int
+    kv_heads: int
+    head_dim: int
+    head_stride: int
+    k_offset: int
+    v_offset: int
+    causal: bool
+
+    @classmethod
+    def neox(cls, t):
+        """GPTNeoX: q | k | v interleaved per head."""
+        H, D = t.heads, t.head_dim
+        return cls(H, H, D, 3 * D, D, 2 * D, True)
+
+    @classmethod
+    def gqa(cls, t):
+        """Llama: every q head, then the kv_heads k heads, then the v heads."""
+        H, Hk, D = t.heads, t.n_kv, t.head_dim
+        return cls(H, Hk, D, D, H * D, (H + Hk) * D, True)
+
+    @classmethod
+    def planar(cls, c):
+        """ViT / RoBERTa: q | k | v, each `hidden` wide; bidirectional."""
+        return cls(c.heads, c.heads, c.head_dim, c.head_dim, c.hidden, 2 * c.hidden, False)
 
 
 class Batch:
@@ -511,6 +546,13 @@ def _to(t: torch.Tensor, device: torch.device, dtype) -> torch.Tensor:
     return t.to(device)
 
 
+def _drop_geometry(vl: Batch | None, B: int, S: int) -> dict:
+    """The geometry keywords of K.attention_drop_fwd / _bwd: dense, or varlen over the batch vl."""
+    if vl is None:
+        return dict(batch=B, seq=S)
+    return dict(lens=vl.lens, cu_seqlens=vl.cu_seqlens, max_seq=S)
+
+
 class Engine:
     def __init__(self, cfg: ModelConfig, store: ParamStore, max_seq: int = 4096):
         self.cfg = cfg
@@ -525,6 +567,25 @@ class Engine:
                 cos, sin = rope_tables(t.hidden, t.heads, t.rotary_pct, t.rope_theta, max_seq)
             self.cos = cos.to(self.dev)
             self.sin = sin.to(self.dev)
+        # the family's whole-model (forward, backward), and for the causal LMs the layer pair
+        if cfg.convnext is not None:
+            self._family = (self._convnext_forward, self._convnext_backward)
+        elif cfg.classifier:
+            self._family = (self._cls_forward, self._cls_backward)
+        elif t.roberta:
+            self._family = (self._roberta_forward, self._roberta_backward)
+        else:
+            self._family = (self._causal_forward, self._causal_backward)
+            self._layer = (self._llama_layer_fwd, self._llama_layer_bwd) if t.llama else \
+                (self._mamba_layer_fwd, self._mamba_layer_bwd) if t.mamba else \
+                (self._text_layer_fwd, self._text_layer_bwd)
+        # the qkv layouts of the text layers and of the ViT layers (_attention_fwd / _bwd)
+        self._attn_t = self._attn_v = None
+        if t is not None and not t.mamba:
+            self._attn_t = AttnLayout.gqa(t) if t.llama else AttnLayout.planar(t) if t.roberta \
+                else AttnLayout.neox(t)
+        if cfg.multimodal:
+            self._attn_v = AttnLayout.planar(cfg.vision)
         self.cache: dict = {}
         # activation checkpointing (HF gradient_checkpointing, src/train.py:112 →
         # TrainingClass.gradient_checkpointing): keep only each layer's input residual
@@ -817,13 +878,119 @@ class Engine:
             torch.cuda.current_stream(self.dev).wait_stream(self._side)
             self._fences, self._pending = [], []
 
-    # -------------------------------------------------------------- text layers
-    # Padded batches (Batch.cu_seqlens set): the text layers run over the T valid tokens.  Every
-    # buffer is sized by the residual stream's row count, `S` is the longest sequence
-    # (Batch.max_len: the varlen kernels' max_seq and the lse stride), attention takes the
-    # varlen entries and the rope reads each token's position from Batch.pos.  _vl is the
-    # batch of the forward / backward in flight, or None on the dense path.
+    # -------------------------------------------------------------- the step frame
+    # What every family's forward and backward share.  Padded and packed batches
+    # (Batch.cu_seqlens set): the text layers run over the T valid tokens.  Every buffer is sized
+    # by the residual stream's row count, `S` is the longest sequence (Batch.max_len: the varlen
+    # kernels' max_seq and the lse stride), attention, the Mamba conv and the scan take their
+    # varlen entries and the rope reads each token's position from Batch.pos.  _vl is the batch
+    # of the forward / backward in flight, or None on the dense path (image batches always).
     _vl = None
+
+    def _begin(self, batch: Batch, need_grad: bool) -> None:
+        """The forward's prologue: the varlen state, the staged batch handed to the compute
+        stream, the residency region, the micro-step's dropout state (the image classifiers
+        draw no embedding noise)."""
+        self._vl = batch if batch.cu_seqlens is not None else None
+        if self.dev.type == "cuda":
+            batch.use(torch.cuda.current_stream(self.dev))
+        region = getattr(self.units, "region", None)
+        if region is not None:  # an overlapped optimizer update of the fp32-read region
+            region()
+        if self.cos is not None and batch.max_len > self.cos.shape[0]:
+            raise ValueError(f"sequence {batch.max_len} longer than the rope table "
+                             f"{self.cos.shape[0]}")
+        self._drop_begin(need_grad, None if self.cfg.classifier else batch)
+
+    def _loss(self, logits, batch: Batch, vocab_valid: int, grad_scale: float,
+              need_grad: bool) -> torch.Tensor:
+        """Σ_rows CE over the bf16 logits (device fp32 [1]), the forward's last act.  With
+        need_grad the logits become dlogits in place and the cache entries the family has set
+        stay for the backward; without, nothing of the step is kept."""
+        loss_rows = self._e(logits.shape[0], dtype=F32)
+        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
+                        logits if need_grad else None, vocab_valid=vocab_valid,
+                        label_smoothing=self.label_smoothing)
+        loss = self._e(1, dtype=F32)
+        K.sum_f32(loss_rows, loss)
+        if not need_grad:
+            self.cache.clear()
+        return loss
+
+    def _begin_backward(self, batch: Batch, scale: torch.Tensor | None) -> tuple:
+        """The backward's prologue: the head's cache entry, its last element the dlogits
+        (times `scale`)."""
+        self._vl = batch if batch.cu_seqlens is not None else None
+        head = self.cache.pop("head")
+        if scale is not None:
+            head[-1].mul_(scale.to(torch.float32))
+        return head
+
+    def _finish(self) -> None:
+        """The backward's epilogue."""
+        self._join_side()
+        self.cache.clear()
+
+    def _scored_rows(self, y, batch: Batch):
+        """Loss-row compaction: the rows of y that carry a label (y itself when most do)."""
+        if batch.loss_rows is None:
+            return y
+        yv = self._e(batch.loss_rows.numel(), y.shape[1])
+        K.gather_rows(y, batch.loss_rows, yv)
+        return yv
+
+    def _all_rows(self, dy, batch: Batch):
+        """Backward of _scored_rows: back to every row, zero where the label is ignored."""
+        if batch.loss_map is None:
+            return dy
+        out = self._e(batch.T, dy.shape[1])
+        K.expand_rows(dy, batch.loss_map, out)
+        return out
+
+    # -------------------------------------------------------------- attention
+    def _attention_fwd(self, lay: AttnLayout, unit: int, p: float, qkv, B, S, a, lse,
+                       vl: Batch | None = None) -> None:
+        """Attention of every transformer layer: with probability dropout p at site k = 2 of
+        `unit` (the checkpoint recompute redraws the same mask), varlen over the batch vl, GQA or
+        plain.  The vision tower passes no vl: images are dense whatever the text batch is."""
+        H, Hk, D, hs, koff, voff, causal = lay
+        sc = D ** -0.5
+        if p > 0:
+            K.attention_drop_fwd(qkv, H, Hk, D, hs, koff, voff, causal, sc, a, lse, p,
+                                 self.dropout_seed, self._site(unit, 2),
+                                 **_drop_geometry(vl, B, S))
+        elif vl is not None:
+            K.attention_varlen_fwd(qkv, vl.lens, vl.cu_seqlens, H, Hk, D, hs, koff, voff, causal,
+                                   sc, a, lse, max_seq=S)
+        elif Hk != H:
+            K.attention_gqa_fwd(qkv, B, S, H, Hk, D, koff, voff, causal, sc, a, lse)
+        else:
+            K.attention_fwd(qkv, B, S, H, D, hs, koff, causal, sc, a, lse)
+
+    def _attention_bwd(self, lay: AttnLayout, unit: int, p: float, qkv, B, S, a, da, lse, dqkv,
+                       rot_dims: int = 0, vl: Batch | None = None) -> None:
+        """Backward of _attention_fwd (same site).  rot_dims > 0 (GPTNeoX): also the rope backward
+        of dqkv's q and k parts — in the dK / dQ epilogues of the dense entry, a pass of its own
+        after the dropout and varlen entries (ring dK/dV + recomputing dQ), which fuse none."""
+        H, Hk, D, hs, koff, voff, causal = lay
+        sc = D ** -0.5
+        if p > 0:
+            K.attention_drop_bwd(qkv, H, Hk, D, hs, koff, voff, causal, sc, a, da, lse, dqkv, p,
+                                 self.dropout_seed, self._site(unit, 2),
+                                 **_drop_geometry(vl, B, S))
+        elif vl is not None:
+            K.attention_varlen_bwd(qkv, vl.lens, vl.cu_seqlens, H, Hk, D, hs, koff, voff, causal,
+                                   sc, a, da, lse, dqkv, max_seq=S)
+        elif rot_dims > 0:
+            K.attention_bwd_rope(qkv, B, S, H, D, hs, koff, causal, sc, a, da, lse, dqkv,
+                                 rot_dims, self.cos, self.sin)
+            return
+        elif Hk != H:
+            K.attention_gqa_bwd(qkv, B, S, H, Hk, D, koff, voff, causal, sc, a, da, lse, dqkv)
+        else:
+            K.attention_bwd(qkv, B, S, H, D, hs, koff, causal, sc, a, da, lse, dqkv)
+        if rot_dims > 0:
+            self._rope(dqkv, S, H, D, rot_dims, hs, koff, inverse=True)
 
     def _rope(self, qkv, S, heads, D, rot, head_stride, part_stride, inverse=False, parts=2,
               offset=0):
@@ -869,22 +1036,7 @@ class Engine:
         K.colsum(out, self.s.g(bias), accumulate=True)
         return out
 
-    def _attn_drop_fwd(self, pa, unit, vl, qkv, B, S, H, Hk, D, hs, koff, voff, causal, a, lse):
-        """Attention with probability dropout pa at site k = 2 of `unit` (dense, or varlen over
-        the batch vl): the forward, and the checkpoint recompute, which redraws the same mask."""
-        geo = dict(batch=B, seq=S) if vl is None else \
-            dict(lens=vl.lens, cu_seqlens=vl.cu_seqlens, max_seq=S)
-        K.attention_drop_fwd(qkv, H, Hk, D, hs, koff, voff, causal, D ** -0.5, a, lse, pa,
-                             self.dropout_seed, self._site(unit, 2), **geo)
-
-    def _attn_drop_bwd(self, pa, unit, vl, qkv, B, S, H, Hk, D, hs, koff, voff, causal, a, da, lse,
-                       dqkv):
-        """Backward of _attn_drop_fwd (same site); the caller runs the rope inverse afterwards."""
-        geo = dict(batch=B, seq=S) if vl is None else \
-            dict(lens=vl.lens, cu_seqlens=vl.cu_seqlens, max_seq=S)
-        K.attention_drop_bwd(qkv, H, Hk, D, hs, koff, voff, causal, D ** -0.5, a, da, lse, dqkv,
-                             pa, self.dropout_seed, self._site(unit, 2), **geo)
-
+    # -------------------------------------------------------------- text layers
     def _text_layer_fwd(self, i, x, B, S):
         t = self.cfg.text
         T, h, H, D = x.shape[0], t.hidden, t.heads, t.head_dim
@@ -898,15 +1050,7 @@ class Engine:
             self._rope(qkv, S, H, D, t.rot_dims, 3 * D, D)
         a = self._e(T, h)
         lse = self._e(B * H * S, dtype=F32)
-        vl = self._vl
-        if self._pat > 0:
-            self._attn_drop_fwd(self._pat, 1 + i, vl, qkv, B, S, H, H, D, 3 * D, D, 2 * D, True, a,
-                                lse)
-        elif vl is None:
-            K.attention_fwd(qkv, B, S, H, D, 3 * D, D, True, D ** -0.5, a, lse)
-        else:
-            K.attention_varlen_fwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, 3 * D, D, 2 * D, True,
-                                   D ** -0.5, a, lse, max_seq=S)
+        self._attention_fwd(self._attn_t, 1 + i, self._pat, qkv, B, S, a, lse, vl=self._vl)
         ap = self._linear(a, p + "dense")
         pre, act = self._e(T, t.ffn), self._e(T, t.ffn)
         self._linear(y2, p + "fc1", out=pre, epi=K.EPI_BF16_GELU, out2=act)
@@ -924,14 +1068,13 @@ class Engine:
             self.cache[("t", i)] = (x, mean, rstd, y1, y2, qkv, a, lse, pre, act)
         return xn
 
-    def _resid_grad_targets(self, i):
-        """bf16 copy + bias-gradient targets for text layer i's residual-stream gradient:
-        d(fc2.bias) == d(dense.bias) == Σ bf16(dh) under the parallel residual."""
+    def _resid_grad_targets(self, i, T):
+        """bf16 copy + bias-gradient targets for text layer i's residual-stream gradient (T
+        rows): d(fc2.bias) == d(dense.bias) == Σ bf16(dh) under the parallel residual."""
         if i < 0:
             return {}
         p = f"text.layers.{i}."
         self._grad_open(f"text.layers.{i}")
-        T = self._T
         if self._pt > 0:  # the two biases then see differently masked gradients (_drop_grad)
             return dict(dx_bf16=self._e(T, self.cfg.text.hidden))
         return dict(dx_bf16=self._e(T, self.cfg.text.hidden), dsum=self.s.g(p + "fc2.bias"),
@@ -942,7 +1085,7 @@ class Engine:
         (mlp + attn) sum, produced (with the fc2/dense bias gradients) by the layer
         above's fused LayerNorm backward."""
         t = self.cfg.text
-        T, h, H, D = dxn.shape[0], t.hidden, t.heads, t.head_dim
+        T, h = dxn.shape[0], t.hidden
         p = f"text.layers.{i}."
         self._side_fence()
         self._unit_bwd(f"text.layers.{i}")
@@ -959,26 +1102,12 @@ class Engine:
         da = self._dx(dsa, p + "dense")
         self._dw(dsa, a, p + "dense", bias=False)
         dqkv = self._e(T, 3 * h)
-        vl = self._vl
-        if self._pat > 0:  # dropout: no fused rope backward, the rope inverse runs afterwards
-            self._attn_drop_bwd(self._pat, 1 + i, vl, qkv, B, S, H, H, D, 3 * D, D, 2 * D, True, a,
-                                da, lse, dqkv)
-            if t.rot_dims > 0:
-                self._rope(dqkv, S, H, D, t.rot_dims, 3 * D, D, inverse=True)
-        elif vl is not None:  # varlen: ring dK/dV + recomputing dQ, then the positional rope
-            K.attention_varlen_bwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, 3 * D, D, 2 * D, True,
-                                   D ** -0.5, a, da, lse, dqkv, max_seq=S)
-            if t.rot_dims > 0:
-                self._rope(dqkv, S, H, D, t.rot_dims, 3 * D, D, inverse=True)
-        elif t.rot_dims > 0:  # + the rope backward (in the dK / dQ epilogues at D = 256)
-            K.attention_bwd_rope(qkv, B, S, H, D, 3 * D, D, True, D ** -0.5, a, da, lse, dqkv,
-                                 t.rot_dims, self.cos, self.sin)
-        else:
-            K.attention_bwd(qkv, B, S, H, D, 3 * D, D, True, D ** -0.5, a, da, lse, dqkv)
+        self._attention_bwd(self._attn_t, 1 + i, self._pat, qkv, B, S, a, da, lse, dqkv,
+                            rot_dims=t.rot_dims, vl=self._vl)
         dy1 = self._dx(dqkv, p + "qkv")
         self._dw(dqkv, y1, p + "qkv")
         # dx = dxn + LN1'(dy1) + LN2'(dy2)  (in place over dxn), + bf16 copy for layer i-1
-        nxt = self._resid_grad_targets(i - 1)
+        nxt = self._resid_grad_targets(i - 1, T)
         K.layernorm_bwd(x, mean, rstd, dy1, self.s.p(p + "ln1.weight"), dxn,
                         self.s.g(p + "ln1.weight"), self.s.g(p + "ln1.bias"), dy2,
                         self.s.p(p + "ln2.weight"), self.s.g(p + "ln2.weight"),
@@ -1002,15 +1131,7 @@ class Engine:
         self._rope(qkv, S, Hk, D, D, D, 0, parts=1, offset=H * D)
         a = self._e(T, h)
         lse = self._e(B * H * S, dtype=F32)
-        vl = self._vl
-        if self._pat > 0:
-            self._attn_drop_fwd(self._pat, 1 + i, vl, qkv, B, S, H, Hk, D, D, H * D, (H + Hk) * D,
-                                True, a, lse)
-        elif vl is None:
-            K.attention_gqa_fwd(qkv, B, S, H, Hk, D, H * D, (H + Hk) * D, True, D ** -0.5, a, lse)
-        else:
-            K.attention_varlen_fwd(qkv, vl.lens, vl.cu_seqlens, H, Hk, D, D, H * D, (H + Hk) * D,
-                                   True, D ** -0.5, a, lse, max_seq=S)
+        self._attention_fwd(self._attn_t, 1 + i, self._pat, qkv, B, S, a, lse, vl=self._vl)
         h1 = self._linear(a, p + "dense", bias=False, epi=K.EPI_F32_RESID, out2=x)
         y2, r2 = self._e(T, h), self._e(T, dtype=F32)
         K.rmsnorm_fwd(h1, self.s.p(p + "ln2.weight"), t.eps, y2, r2)
@@ -1046,16 +1167,8 @@ class Engine:
         da = self._dx(d1, p + "dense")
         self._dw(d1, a, p + "dense", bias=False)
         dqkv = self._e(T, t.qkv_dim)
-        vl = self._vl
-        if self._pat > 0:
-            self._attn_drop_bwd(self._pat, 1 + i, vl, qkv, B, S, H, Hk, D, D, H * D, (H + Hk) * D,
-                                True, a, da, lse, dqkv)
-        elif vl is None:
-            K.attention_gqa_bwd(qkv, B, S, H, Hk, D, H * D, (H + Hk) * D, True, D ** -0.5, a, da,
-                                lse, dqkv)
-        else:
-            K.attention_varlen_bwd(qkv, vl.lens, vl.cu_seqlens, H, Hk, D, D, H * D, (H + Hk) * D,
-                                   True, D ** -0.5, a, da, lse, dqkv, max_seq=S)
+        self._attention_bwd(self._attn_t, 1 + i, self._pat, qkv, B, S, a, da, lse, dqkv,
+                            vl=self._vl)
         self._rope(dqkv, S, H, D, D, D, 0, inverse=True, parts=1)
         self._rope(dqkv, S, Hk, D, D, D, 0, inverse=True, parts=1, offset=H * D)
         dy1 = self._dx(dqkv, p + "qkv")
@@ -1069,7 +1182,7 @@ class Engine:
     # -------------------------------------------------------------- vision
     def _vit_layer_fwd(self, i, x, B, Sv):
         v = self.cfg.vision
-        T, h, H, D = B * Sv, v.hidden, v.heads, v.head_dim
+        T, h, H = B * Sv, v.hidden, v.heads
         p = f"vision.layers.{i}."
         y1 = self._e(T, h)
         m1, r1 = self._e(T, dtype=F32), self._e(T, dtype=F32)
@@ -1078,10 +1191,7 @@ class Engine:
         a = self._e(T, h)
         lse = self._e(B * H * Sv, dtype=F32)
         pv, u = self._pv, VISION_UNIT + 1 + i
-        if self._pav > 0:
-            self._attn_drop_fwd(self._pav, u, None, qkv, B, Sv, H, H, D, D, h, 2 * h, False, a, lse)
-        else:
-            K.attention_fwd(qkv, B, Sv, H, D, D, h, False, D ** -0.5, a, lse)
+        self._attention_fwd(self._attn_v, u, self._pav, qkv, B, Sv, a, lse)
         if pv > 0:  # h1 = x + drop(o): ViTSelfOutput.dropout
             h1 = self._e(T, h, dtype=F32)
             K.dropout_add_f32(self._linear(a, p + "o"), self._site(u, 0), x, h1, pv,
@@ -1112,7 +1222,7 @@ class Engine:
         """d2 = bf16(dxn) with fc2.bias's gradient already accumulated (by the layer
         above's fused LN backward, or the caller for the top layer)."""
         v = self.cfg.vision
-        T, h, H, D = B * Sv, v.hidden, v.heads, v.head_dim
+        T, h = B * Sv, v.hidden
         p = f"vision.layers.{i}."
         self._side_fence()
         self._unit_bwd(f"vision.layers.{i}")
@@ -1135,11 +1245,7 @@ class Engine:
         da = self._dx(d1, p + "o")
         self._dw(d1, a, p + "o", bias=False)
         dqkv = self._e(T, 3 * h)
-        if self._pav > 0:
-            self._attn_drop_bwd(self._pav, u, None, qkv, B, Sv, H, H, D, D, h, 2 * h, False, a, da,
-                                lse, dqkv)
-        else:
-            K.attention_bwd(qkv, B, Sv, H, D, D, h, False, D ** -0.5, a, da, lse, dqkv)
+        self._attention_bwd(self._attn_v, u, self._pav, qkv, B, Sv, a, da, lse, dqkv)
         dy1 = self._dx(dqkv, p + "qkv")
         self._dw(dqkv, y1, p + "qkv")
         if i > 0:
@@ -1249,13 +1355,7 @@ class Engine:
         the CLS rows (the only ones the head reads), classifier with its bias, Σ_images CE."""
         cfg, v = self.cfg, self.cfg.vision
         B, Sv = batch.B, v.num_patches + 1
-        self._vl = None
-        if self.dev.type == "cuda":
-            batch.use(torch.cuda.current_stream(self.dev))
-        region = getattr(self.units, "region", None)
-        if region is not None:
-            region()
-        self._drop_begin(need_grad)
+        self._begin(batch, need_grad)
         h, cols, pre_ln = self._encoder_fwd(batch.pixels, B)
         y = self._e(B, v.hidden)
         m, r = self._e(B, dtype=F32), self._e(B, dtype=F32)
@@ -1263,27 +1363,15 @@ class Engine:
                      v.eps, y, m, r)
         self._unit_fwd("cls_head")
         logits = self._linear(y, "cls_head")
-        loss_rows = self._e(B, dtype=F32)
-        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=cfg.num_classes,
-                        label_smoothing=self.label_smoothing)
-        loss = self._e(1, dtype=F32)
-        K.sum_f32(loss_rows, loss)
-        if need_grad:
-            self.cache["head"] = (h, m, r, y, logits)
-            self.cache["vis"] = (cols, pre_ln)
-        else:
-            self.cache.clear()
-        return loss
+        self.cache["head"] = (h, m, r, y, logits)
+        self.cache["vis"] = (cols, pre_ln)
+        return self._loss(logits, batch, cfg.num_classes, grad_scale, need_grad)
 
     def _cls_backward(self, batch: Batch, scale: torch.Tensor | None) -> None:
         v = self.cfg.vision
         B, Sv = batch.B, v.num_patches + 1
-        self._vl = None
-        hL, m, r, y, dlogits = self.cache.pop("head")
+        hL, m, r, y, dlogits = self._begin_backward(batch, scale)
         cols, pre_ln = self.cache.pop("vis")
-        if scale is not None:
-            dlogits.mul_(scale.to(torch.float32))
         self._unit_bwd("cls_head")
         dy = self._dx(dlogits, "cls_head")
         self._dw(dlogits, y, "cls_head")  # + the classifier's bias gradient
@@ -1300,8 +1388,7 @@ class Engine:
                      dsum=None if self._pv > 0 else self.s.g(top + ".fc2.bias"))
         self._encoder_bwd(dh, d2, B, cols, pre_ln)
         self._ready(("vision.", "cls_head."))
-        self._join_side()
-        self.cache.clear()
+        self._finish()
 
     # -------------------------------------------------------------- ConvNeXt
     # The residual stream x is fp32 [B·H·W, C], channels-last.  A block keeps (x, c, mean, rstd,
@@ -1310,6 +1397,7 @@ class Engine:
     # ConvNextEncoderWithCheckpointing wraps each ConvNextStage).  Stochastic depth
     # (drop_path_rate > 0, training): a block with drop probability > 0 runs over its kept samples
     # only (_cn_block_drop_fwd / _bwd) and additionally keeps their map and its probability.
+    # _convnext_forward / _backward are the family's body inside the step frame.
     def _cn_f32_of_bf16(self, x, name):
         """f32(bf16(x·Wᵀ + b)): a conv output (bf16 under autocast) held exactly in the fp32
         stream — the residual epilogue over a zero residual."""
@@ -1484,13 +1572,7 @@ class Engine:
         average pool, LayerNorm (head_eps), the classifier with its bias, Σ_images CE."""
         cfg, cn = self.cfg, self.cfg.convnext
         B, C0, C3 = batch.B, cn.hidden_sizes[0], cn.hidden_sizes[-1]
-        self._vl = None
-        if self.dev.type == "cuda":
-            batch.use(torch.cuda.current_stream(self.dev))
-        region = getattr(self.units, "region", None)
-        if region is not None:
-            region()
-        self._drop_begin(need_grad)
+        self._begin(batch, need_grad)
         R0 = B * cn.side(0) ** 2
         cols = self._e(R0, cn.patch_k)
         K.im2col(batch.pixels, cn.patch, cols)
@@ -1512,27 +1594,15 @@ class Engine:
                         self.s.p("convnext.ln_post.bias"), cn.head_eps, y, m, r)
         self._unit_fwd("cls_head")
         logits = self._linear(y, "cls_head")
-        loss_rows = self._e(B, dtype=F32)
-        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=cfg.num_classes,
-                        label_smoothing=self.label_smoothing)
-        loss = self._e(1, dtype=F32)
-        K.sum_f32(loss_rows, loss)
-        if need_grad:
-            self.cache["head"] = (pooled, m, r, y, logits)
-            self.cache["stem"] = (cols, po, m0, r0)
-        else:
-            self.cache.clear()
-        return loss
+        self.cache["head"] = (pooled, m, r, y, logits)
+        self.cache["stem"] = (cols, po, m0, r0)
+        return self._loss(logits, batch, cfg.num_classes, grad_scale, need_grad)
 
     def _convnext_backward(self, batch: Batch, scale: torch.Tensor | None) -> None:
         cn = self.cfg.convnext
         B, C0, C3 = batch.B, cn.hidden_sizes[0], cn.hidden_sizes[-1]
-        self._vl = None
-        pooled, m, r, y, dlogits = self.cache.pop("head")
+        pooled, m, r, y, dlogits = self._begin_backward(batch, scale)
         cols, po, m0, r0 = self.cache.pop("stem")
-        if scale is not None:
-            dlogits.mul_(scale.to(torch.float32))
         self._unit_bwd("cls_head")
         dy = self._dx(dlogits, "cls_head")
         self._dw(dlogits, y, "cls_head")  # + the classifier's bias gradient
@@ -1558,39 +1628,15 @@ class Engine:
         self._dw(dpb, cols, "convnext.stem")
         self._unit_done("convnext.stem")
         self._ready(("convnext.stem.", "convnext.stem_ln."))
-        self._join_side()
-        self.cache.clear()
+        self._finish()
 
     # -------------------------------------------------------------- RoBERTa (post-LN encoder)
     # The stream between sub-layers is fp32 AND normalised: each sub-layer ends in
     # LayerNorm(dropout(branch) + input) (include/mmpt.h K20).  A layer's input is the pair
     # (h32, h16 = bf16(h32)): h32 feeds the residual add, h16 the GEMMs.  Kept for the backward,
     # per sub-layer: the sum s the LayerNorm read (fp32), its statistics and its bf16 output; the
-    # fp32 output lives only until the next add.
-    def _roberta_attn(self, i, qkv, B, S, a, lse, da=None, dqkv=None):
-        """Non-causal attention over q | k | v (each `hidden` wide, head h at h * D), as the ViT
-        layer calls it: dense, varlen over a right-padded batch, or with probability dropout."""
-        t = self.cfg.text
-        h, H, D = t.hidden, t.heads, t.head_dim
-        vl, sc = self._vl, D ** -0.5
-        if da is None:
-            if self._pat > 0:
-                self._attn_drop_fwd(self._pat, 1 + i, vl, qkv, B, S, H, H, D, D, h, 2 * h, False, a,
-                                    lse)
-            elif vl is None:
-                K.attention_fwd(qkv, B, S, H, D, D, h, False, sc, a, lse)
-            else:
-                K.attention_varlen_fwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, D, h, 2 * h, False, sc,
-                                       a, lse, max_seq=S)
-        elif self._pat > 0:
-            self._attn_drop_bwd(self._pat, 1 + i, vl, qkv, B, S, H, H, D, D, h, 2 * h, False, a, da,
-                                lse, dqkv)
-        elif vl is None:
-            K.attention_bwd(qkv, B, S, H, D, D, h, False, sc, a, da, lse, dqkv)
-        else:
-            K.attention_varlen_bwd(qkv, vl.lens, vl.cu_seqlens, H, H, D, D, h, 2 * h, False, sc, a,
-                                   da, lse, dqkv, max_seq=S)
-
+    # fp32 output lives only until the next add.  Attention is _attention_fwd / _bwd over the
+    # planar layout; _roberta_forward / _backward are the family's body inside the step frame.
     def _roberta_layer_fwd(self, i, x, B, S):
         """RobertaLayer (tf:models/roberta/modeling_roberta.py) under autocast:
         h1 = LN1(f32(drop(dense(attn(bf16 x)))) + x);  h2 = LN2(f32(drop(fc2(gelu(fc1(bf16 h1))))) + h1)."""
@@ -1603,7 +1649,7 @@ class Engine:
         qkv = self._linear(x16, p + "qkv")
         a = self._e(T, h)
         lse = self._e(B * H * S, dtype=F32)
-        self._roberta_attn(i, qkv, B, S, a, lse)
+        self._attention_fwd(self._attn_t, 1 + i, self._pat, qkv, B, S, a, lse, vl=self._vl)
         ao = self._linear(a, p + "dense")
         # the sum may overwrite the input stream unless that is this layer's checkpoint
         s1 = self._e(T, h, dtype=F32) if ckpt else x32
@@ -1653,7 +1699,8 @@ class Engine:
         da = self._dx(do, p + "dense")
         self._dw(do, a, p + "dense", bias=False)
         dqkv = self._e(T, 3 * h)
-        self._roberta_attn(i, qkv, B, S, a, lse, da, dqkv)
+        self._attention_bwd(self._attn_t, 1 + i, self._pat, qkv, B, S, a, da, lse, dqkv,
+                            vl=self._vl)
         dx16 = self._dx(dqkv, p + "qkv")
         self._dw(dqkv, x16, p + "qkv")
         self._unit_done(f"text.layers.{i}")
@@ -1665,13 +1712,7 @@ class Engine:
         (the tied embedding) with its bias, Σ CE over the real vocabulary."""
         t = self.cfg.text
         B, S, T, h = batch.B, batch.max_len, batch.T, t.hidden
-        self._vl = batch if batch.cu_seqlens is not None else None
-        if self.dev.type == "cuda":
-            batch.use(torch.cuda.current_stream(self.dev))
-        region = getattr(self.units, "region", None)
-        if region is not None:
-            region()
-        self._drop_begin(need_grad, batch)
+        self._begin(batch, need_grad)
         h32, h16 = self._e(T, h, dtype=F32), self._e(T, h)
         m0, r0 = self._e(T, dtype=F32), self._e(T, dtype=F32)
         K.roberta_embed_fwd(batch.ids, batch.pos_ids, self.s.p("text.embed"),
@@ -1684,10 +1725,7 @@ class Engine:
             self._unit_fwd(f"text.layers.{i}")
             x = self._roberta_layer_fwd(i, x, B, S)
         self._unit_fwd("text.mlm")
-        xv = x[1]
-        if batch.loss_rows is not None:  # the head reads the labelled rows only
-            xv = self._e(batch.loss_rows.numel(), h)
-            K.gather_rows(x[1], batch.loss_rows, xv)
+        xv = self._scored_rows(x[1], batch)  # the head reads the labelled rows only
         R = xv.shape[0]
         pre, gl = self._e(R, h), self._e(R, h)
         self._linear(xv, "text.mlm.dense", out=pre, epi=K.EPI_BF16_GELU, out2=gl)
@@ -1697,27 +1735,15 @@ class Engine:
                      mh, rh)
         logits = self._e(R, t.vocab)
         K.gemm(n16, self.s.w("text.embed"), logits, bias=self.s.w("text.mlm.bias"))
-        loss_rows = self._e(R, dtype=F32)
-        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=t.n_vocab,
-                        label_smoothing=self.label_smoothing)
-        loss = self._e(1, dtype=F32)
-        K.sum_f32(loss_rows, loss)
-        if need_grad:
-            self.cache["head"] = (xv, pre, gl, mh, rh, n16, logits)
-            self.cache["emb"] = (m0, r0)
-        else:
-            self.cache.clear()
-        return loss
+        self.cache["head"] = (xv, pre, gl, mh, rh, n16, logits)
+        self.cache["emb"] = (m0, r0)
+        return self._loss(logits, batch, t.n_vocab, grad_scale, need_grad)
 
     def _roberta_backward(self, batch: Batch, scale: torch.Tensor | None) -> None:
         t = self.cfg.text
-        B, S, T, h = batch.B, batch.max_len, batch.T, t.hidden
-        self._vl = batch if batch.cu_seqlens is not None else None
-        xv, pre, gl, mh, rh, n16, dlogits = self.cache.pop("head")
+        B, S, h = batch.B, batch.max_len, t.hidden
+        xv, pre, gl, mh, rh, n16, dlogits = self._begin_backward(batch, scale)
         m0, r0 = self.cache.pop("emb")
-        if scale is not None:
-            dlogits.mul_(scale.to(torch.float32))
         g = self.s.g
         self._unit_bwd("text.mlm")
         dn = self._dx(dlogits, "text.embed")  # through E^T (the decoder is the tied embedding)
@@ -1731,9 +1757,7 @@ class Engine:
         dyb = self._dx(dpre, "text.mlm.dense")
         self._dw(dpre, xv, "text.mlm.dense", bias=False)
         self._unit_done("text.mlm")
-        if batch.loss_map is not None:  # back to every row (zero where there is no label)
-            dyc, dyb = dyb, self._e(T, h)
-            K.expand_rows(dyc, batch.loss_map, dyb)
+        dyb = self._all_rows(dyb, batch)
         d32 = None
         for i in reversed(range(t.layers)):
             d32, dyb = self._roberta_layer_bwd(i, d32, dyb, B, S)
@@ -1750,11 +1774,28 @@ class Engine:
         K.embed_bwd(batch.segments, d32, g("text.embed"))
         K.embed_bwd(batch.pos_segments, d32, g("text.pos_embed"))
         self._ready(("text.",))
-        self._join_side()
-        self.cache.clear()
+        self._finish()
 
     # -------------------------------------------------------------- mamba
+    # The blocks only: around them Mamba is the causal-LM step below (_causal_forward / _backward).
     _scan_keep = True  # the forward in flight hands the scan's chunk states to a backward
+
+    def _mamba_conv(self, ops, S, bwd=False, **kw):
+        """The causal conv over `ops`, forward or backward: dense rows of S tokens, or, for packed
+        rows, the varlen entry — each sequence on its own, by Batch.pos."""
+        if self._vl is None:
+            (K.causal_conv1d_bwd if bwd else K.causal_conv1d_fwd)(*ops, S, **kw)
+        else:
+            (K.causal_conv1d_varlen_bwd if bwd else K.causal_conv1d_varlen_fwd)(
+                *ops, self._vl.pos, **kw)
+
+    def _mamba_scan(self, ops, S, bwd=False, **kw):
+        """The selective scan over `ops`, likewise (packed rows: by Batch.scan_tables)."""
+        if self._vl is None:
+            (K.selective_scan_bwd if bwd else K.selective_scan_fwd)(*ops, S, **kw)
+        else:
+            (K.selective_scan_varlen_bwd if bwd else K.selective_scan_varlen_fwd)(
+                *ops, self._vl.scan_tables, **kw)
 
     def _mamba_layer_fwd(self, i, x, B, S):
         """MambaBlock (tf:models/mamba/modeling_mamba.py) with the fused arithmetic of the
@@ -1768,13 +1809,8 @@ class Engine:
         K.rmsnorm_fwd(x, self.s.p(p + "norm.weight"), t.eps, y, r)
         xz = self._linear(y, p + "in_proj", bias=False)
         u = self._e(T, I)
-        vl = self._vl  # packed rows: the varlen entries, each sequence on its own
-        if vl is None:
-            K.causal_conv1d_fwd(xz[:, :I], self.s.w(p + "conv.weight"), self.s.w(p + "conv.bias"),
-                                u, S)
-        else:
-            K.causal_conv1d_varlen_fwd(xz[:, :I], self.s.w(p + "conv.weight"),
-                                       self.s.w(p + "conv.bias"), u, vl.pos)
+        vl = self._vl
+        self._mamba_conv((xz[:, :I], self.s.w(p + "conv.weight"), self.s.w(p + "conv.bias"), u), S)
         proj = self._linear(u, p + "x_proj", bias=False)
         dt = self._e(T, I)
         K.gemm(proj[:, :R], self.s.w(p + "dt_proj.weight"), dt)
@@ -1786,10 +1822,7 @@ class Engine:
         ys = self._e(T, I)
         scan = (u, dt, self.s.p(p + "dt_proj.bias"), self.s.p(p + "A_log"), proj[:, R:R + N],
                 proj[:, R + N:], self.s.p(p + "D"), xz[:, I:], ys)
-        if vl is None:
-            K.selective_scan_fwd(*scan, S, states=states)
-        else:
-            K.selective_scan_varlen_fwd(*scan, vl.scan_tables, states=states)
+        self._mamba_scan(scan, S, states=states)
         xn = self._linear(ys, p + "out_proj", bias=False, epi=K.EPI_F32_RESID, out2=x)
         if ckpt:
             self.cache[("t", i)] = ("ckpt", x)
@@ -1812,15 +1845,11 @@ class Engine:
         self._dw(ds, ys, p + "out_proj", bias=False)
         dxz, dproj = self._e(T, 2 * I), self._e(T, R + 2 * N)
         du, ddt = self._e(T, I), self._e(T, I)
-        vl = self._vl
         scan = (u, dt, self.s.p(p + "dt_proj.bias"), self.s.p(p + "A_log"), proj[:, R:R + N],
                 proj[:, R + N:], self.s.p(p + "D"), xz[:, I:], dys, du, dxz[:, I:], ddt,
                 dproj[:, R:R + N], dproj[:, R + N:], g(p + "A_log"), g(p + "D"),
                 g(p + "dt_proj.bias"))
-        if vl is None:
-            K.selective_scan_bwd(*scan, S, states=states)
-        else:
-            K.selective_scan_varlen_bwd(*scan, vl.scan_tables, states=states)
+        self._mamba_scan(scan, S, bwd=True, states=states)
         K.gemm(ddt, self.s.wt(p + "dt_proj.weight"), dproj[:, :R])
         self._dw(ddt, proj[:, :R], p + "dt_proj", bias=False)
         # u feeds the scan and x_proj: the conv's backward sums the two gradients in fp32
@@ -1828,10 +1857,7 @@ class Engine:
         self._dw(dproj, u, p + "x_proj", bias=False)
         conv = (xz[:, :I], self.s.w(p + "conv.weight"), self.s.w(p + "conv.bias"), du, dxz[:, :I],
                 g(p + "conv.weight"), g(p + "conv.bias"))
-        if vl is None:
-            K.causal_conv1d_bwd(*conv, S, du2=du2)
-        else:
-            K.causal_conv1d_varlen_bwd(*conv, vl.pos, du2=du2)
+        self._mamba_conv(conv, S, bwd=True, du2=du2)
         dy = self._dx(dxz, p + "in_proj")
         self._dw(dxz, y, p + "in_proj", bias=False)
         nxt = self._e(T, h) if i > 0 else None
@@ -1840,101 +1866,16 @@ class Engine:
         self._unit_done(f"text.layers.{i}")
         return dxn, nxt
 
-    def _mamba_forward(self, batch: Batch, grad_scale: float, need_grad: bool) -> torch.Tensor:
-        """MambaForCausalLM: the embedding gather, the blocks, the final RMSNorm, the decoder tied
-        to the embedding, Σ CE over the shifted labels.  need_grad = False keeps no scan states."""
-        t = self.cfg.text
-        B, S, T = batch.B, batch.S, batch.T
-        self._vl = batch if batch.cu_seqlens is not None else None
-        if self.dev.type == "cuda":
-            batch.use(torch.cuda.current_stream(self.dev))
-        region = getattr(self.units, "region", None)
-        if region is not None:
-            region()
-        self._drop_begin(need_grad, batch)
-        self._scan_keep = need_grad
-        h = self._e(T, t.hidden, dtype=F32)
-        self._f32_fwd("text.embed")
-        K.embed_fwd(batch.ids, self.s.p("text.embed"), h, None, None, noise=self._noise)
-        for i in range(t.layers):
-            self._unit_fwd(f"text.layers.{i}")
-            h = self._mamba_layer_fwd(i, h, B, S)
-        self._scan_keep = True  # a checkpoint recompute runs for a backward
-        yf, rf = self._e(T, t.hidden), self._e(T, dtype=F32)
-        K.rmsnorm_fwd(h, self.s.p("text.final_ln.weight"), t.eps, yf, rf)
-        if batch.loss_rows is not None:
-            yv = self._e(batch.loss_rows.numel(), t.hidden)
-            K.gather_rows(yf, batch.loss_rows, yv)
-            yf = yv
-        logits = self._e(yf.shape[0], t.vocab)
-        K.gemm(yf, self.s.w("text.embed"), logits)
-        loss_rows = self._e(yf.shape[0], dtype=F32)
-        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=t.n_vocab,
-                        label_smoothing=self.label_smoothing)
-        loss = self._e(1, dtype=F32)
-        K.sum_f32(loss_rows, loss)
-        if need_grad:
-            self.cache["head"] = (h, rf, yf, logits)
-        else:
-            self.cache.clear()
-        return loss
-
-    def _mamba_backward(self, batch: Batch, scale: torch.Tensor | None) -> None:
-        """Mirrors _mamba_forward; text.embed's gradient is the decoder's weight gradient plus the
-        gather's deterministic scatter-add."""
-        t = self.cfg.text
-        B, S, T = batch.B, batch.S, batch.T
-        self._vl = batch if batch.cu_seqlens is not None else None
-        hL, rf, yf, dlogits = self.cache.pop("head")
-        if scale is not None:
-            dlogits.mul_(scale.to(torch.float32))
-        dyf = self._dx(dlogits, "text.embed")
-        self._dw(dlogits, yf, "text.embed", bias=False)
-        del dlogits
-        if batch.loss_map is not None:
-            dyc, dyf = dyf, self._e(T, t.hidden)
-            K.expand_rows(dyc, batch.loss_map, dyf)
-        dh, ds = torch.empty_like(hL), self._e(T, t.hidden)
-        K.rmsnorm_bwd(hL, rf, dyf, self.s.p("text.final_ln.weight"), dh,
-                      dw=self._gw("text.final_ln"), dx_bf16=ds)
-        self._ready(("text.final_ln.",))
-        for i in reversed(range(t.layers)):
-            dh, ds = self._mamba_layer_bwd(i, dh, ds, B, S)
-            self._ready((f"text.layers.{i}.",))
-        if self._side is not None:  # the decoder's weight gradient also lands in text.embed
-            torch.cuda.current_stream(self.dev).wait_stream(self._side)
-        self._f32_bwd("text.embed")
-        K.embed_bwd(batch.segments, dh, self.s.g("text.embed"), None, None)
-        self._f32_done("text.embed")
-        self._ready(("text.embed",))
-        self._join_side()
-        self.cache.clear()
-
-    # -------------------------------------------------------------- whole model
-    def forward(self, batch: Batch, grad_scale: float, need_grad: bool = True) -> torch.Tensor:
-        """Returns Σ_tokens CE (device fp32 [1]); when need_grad, dlogits are written
-        (scaled by grad_scale = 1/num_items of the global batch) and the caches kept."""
-        if self.cfg.convnext is not None:
-            return self._convnext_forward(batch, grad_scale, need_grad)
-        if self.cfg.classifier:
-            return self._cls_forward(batch, grad_scale, need_grad)
-        if self.cfg.text.roberta:
-            return self._roberta_forward(batch, grad_scale, need_grad)
-        if self.cfg.text.mamba:
-            return self._mamba_forward(batch, grad_scale, need_grad)
+    # -------------------------------------------------------------- causal LMs
+    # GPTNeoX, Llama and Mamba, text-only or (the first two) behind the ViT and the projector:
+    # the embedding gather, the arch's layers (self._layer), the final LayerNorm (GPTNeoX) or
+    # RMSNorm, the lm_head — tied to the embedding or not — over the scored rows, Σ CE over the
+    # shifted labels.
+    def _causal_forward(self, batch: Batch, grad_scale: float, need_grad: bool) -> torch.Tensor:
         cfg, t = self.cfg, self.cfg.text
         # S: the longest sequence — the padded width on the dense path, where T = B * S
         B, S, T = batch.B, batch.max_len, batch.T
-        self._vl = batch if batch.cu_seqlens is not None else None
-        if self.dev.type == "cuda":
-            batch.use(torch.cuda.current_stream(self.dev))
-        region = getattr(self.units, "region", None)
-        if region is not None:  # an overlapped optimizer update of the fp32-read region
-            region()
-        if S > self.cos.shape[0]:
-            raise ValueError(f"sequence {S} longer than the rope table {self.cos.shape[0]}")
-        self._drop_begin(need_grad, batch)
+        self._begin(batch, need_grad)
         img = self._vision_fwd(batch.pixels, B) if cfg.multimodal else None
         h = self._e(T, t.hidden, dtype=F32)
         self._f32_fwd("text.embed")
@@ -1942,54 +1883,30 @@ class Engine:
         K.embed_fwd(batch.ids, self.s.p("text.embed"), h, batch.img_map, img, noise=self._noise)
         if self._pt > 0:  # GPTNeoX emb_dropout, after the image-token merge
             K.dropout_f32(h, h, self._pt, self.dropout_seed, self._site(0, 0))
-        layer_fwd = self._llama_layer_fwd if t.llama else self._text_layer_fwd
+        self._scan_keep = need_grad  # (Mamba: a forward without gradients keeps no scan states)
         for i in range(t.layers):
             self._unit_fwd(f"text.layers.{i}")
-            h = layer_fwd(i, h, batch.n_seq, S)  # (sequences: the documents of packed rows)
-        yf = self._e(T, t.hidden)
-        mf, rf = self._e(T, dtype=F32), self._e(T, dtype=F32)
-        if t.llama:
+            h = self._layer[0](i, h, batch.n_seq, S)  # (sequences: the documents of packed rows)
+        self._scan_keep = True  # a checkpoint recompute runs for a backward
+        yf, mf, rf = self._e(T, t.hidden), None, self._e(T, dtype=F32)
+        if t.llama or t.mamba:
             K.rmsnorm_fwd(h, self.s.p("text.final_ln.weight"), t.eps, yf, rf)
         else:
+            mf = self._e(T, dtype=F32)
             K.layernorm_fwd(h, self.s.p("text.final_ln.weight"), self.s.p("text.final_ln.bias"),
                             t.eps, yf, mf, rf)
-        if batch.loss_rows is not None:  # compact the loss rows (image slots carry no label)
-            yv = self._e(batch.loss_rows.numel(), t.hidden)
-            K.gather_rows(yf, batch.loss_rows, yv)
-            yf = yv
+        yf = self._scored_rows(yf, batch)  # (LLaVA batches: the image slots carry no label)
         logits = self._e(yf.shape[0], t.vocab)
         if self.head == "text.lm_head":
             self._unit_fwd("text.lm_head")
         K.gemm(yf, self.s.w(self.head), logits)
-        loss_rows = self._e(yf.shape[0], dtype=F32)
-        K.cross_entropy(logits, batch.loss_labels, -100, grad_scale, loss_rows,
-                        logits if need_grad else None, vocab_valid=t.n_vocab,
-                        label_smoothing=self.label_smoothing)
-        loss = self._e(1, dtype=F32)
-        K.sum_f32(loss_rows, loss)
-        if need_grad:
-            self.cache["head"] = (h, mf, rf, yf, logits)
-        else:
-            self.cache.clear()
-        return loss
+        self.cache["head"] = (h, mf, rf, yf, logits)
+        return self._loss(logits, batch, t.n_vocab, grad_scale, need_grad)
 
-    def backward(self, batch: Batch, scale: torch.Tensor | None = None) -> None:
-        """Accumulates every parameter gradient into the flat grad buffer.  `scale`
-        (device scalar, e.g. autograd's grad_output) multiplies the loss gradient."""
-        if self.cfg.convnext is not None:
-            return self._convnext_backward(batch, scale)
-        if self.cfg.classifier:
-            return self._cls_backward(batch, scale)
-        if self.cfg.text.roberta:
-            return self._roberta_backward(batch, scale)
-        if self.cfg.text.mamba:
-            return self._mamba_backward(batch, scale)
+    def _causal_backward(self, batch: Batch, scale: torch.Tensor | None) -> None:
         cfg, t = self.cfg, self.cfg.text
         B, S, T = batch.B, batch.max_len, batch.T
-        self._vl = batch if batch.cu_seqlens is not None else None
-        hL, mf, rf, yf, dlogits = self.cache.pop("head")
-        if scale is not None:
-            dlogits.mul_(scale.to(torch.float32))
+        hL, mf, rf, yf, dlogits = self._begin_backward(batch, scale)
         tied = self.head == "text.embed"
         if not tied:
             self._unit_bwd("text.lm_head")
@@ -1998,30 +1915,28 @@ class Engine:
         if not tied:
             self._unit_done("text.lm_head")
         del dlogits
-        if batch.loss_map is not None:  # back to every row (zero where the label is ignored)
-            dyc = dyf
-            dyf = self._e(hL.shape[0], t.hidden)
-            K.expand_rows(dyc, batch.loss_map, dyf)
+        dyf = self._all_rows(dyf, batch)
         dh = torch.empty_like(hL)
-        self._T = T
-        if t.llama:
+        if t.llama or t.mamba:
             ds = self._e(T, t.hidden)
             K.rmsnorm_bwd(hL, rf, dyf, self.s.p("text.final_ln.weight"), dh,
                           dw=self._gw("text.final_ln"), dx_bf16=ds)
-            layer_bwd = self._llama_layer_bwd
         else:
-            top = self._resid_grad_targets(t.layers - 1)
+            top = self._resid_grad_targets(t.layers - 1, T)
             K.layernorm_bwd(hL, mf, rf, dyf, self.s.p("text.final_ln.weight"), dh,
                             self.s.g("text.final_ln.weight"), self.s.g("text.final_ln.bias"), **top)
             ds = top["dx_bf16"]
-            layer_bwd = self._text_layer_bwd
         self._ready(("text.final_ln.",) + (() if tied else ("text.lm_head",)))
         for i in reversed(range(t.layers)):
-            dh, ds = layer_bwd(i, dh, ds, batch.n_seq, S)
+            dh, ds = self._layer[1](i, dh, ds, batch.n_seq, S)
             self._ready((f"text.layers.{i}.",))
         dimg = self._e(B * cfg.vision.num_patches, t.hidden) if cfg.multimodal else None
         if self._pt > 0:
             K.dropout_f32(dh, dh, self._pt, self.dropout_seed, self._site(0, 0))
+        # the tied decoder's weight gradient also lands in text.embed: Mamba waits for it here
+        # (GPTNeoX and Llama leave that order to the layers' _side_fence, as they always have)
+        if t.mamba and self._side is not None:
+            torch.cuda.current_stream(self.dev).wait_stream(self._side)
         self._f32_bwd("text.embed")
         K.embed_bwd(batch.segments, dh, None if self.frozen else self.s.g("text.embed"),
                     batch.img_map, dimg)
@@ -2030,5 +1945,16 @@ class Engine:
         if cfg.multimodal:
             self._vision_bwd(dimg, B)
             self._ready(("vision.", "proj."))
-        self._join_side()
-        self.cache.clear()
+        self._finish()
+
+    # -------------------------------------------------------------- whole model
+    def forward(self, batch: Batch, grad_scale: float, need_grad: bool = True) -> torch.Tensor:
+        """Returns Σ_tokens CE (device fp32 [1]); when need_grad, dlogits are written
+        (scaled by grad_scale = 1/num_items of the global batch) and the caches kept."""
+        return self._family[0](batch, grad_scale, need_grad)
+
+    def backward(self, batch: Batch, scale: torch.Tensor | None = None) -> None:
+        """Accumulates every parameter gradient into the flat grad buffer.  `scale`
+        (device scalar, e.g. autograd's grad_output) multiplies the loss gradient."""
+        self._family[1](batch, scale)
+

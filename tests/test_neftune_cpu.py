@@ -220,7 +220,17 @@ def test_engine_default_and_wrappers():
     for fn in (K.embed_fwd, K.roberta_embed_fwd, K.roberta_embed_bwd):
         assert inspect.signature(fn).parameters["noise"].default is None
     src = inspect.getsource(Engine)
-    assert src.count("noise=self._noise") == 4  # three forwards and the RoBERTa backward
+    # every call of a noisy kernel passes the noise: the causal-LM and RoBERTa forwards and the
+    # RoBERTa backward (which re-gathers the noisy sum)
+    sites = [m.end() for m in re.finditer(r"K\.(?:embed_fwd|roberta_embed_fwd|roberta_embed_bwd)\(",
+                                          src)]
+    assert len(sites) >= 3 and src.count("noise=self._noise") == len(sites)
+    for at in sites:  # ... each inside its own parentheses
+        depth, end = 1, at
+        while depth:
+            depth += {"(": 1, ")": -1}.get(src[end], 0)
+            end += 1
+        assert "noise=self._noise" in src[at:end], src[at:end]
     assert "self.neftune_alpha: float | None = None" in src
 
 

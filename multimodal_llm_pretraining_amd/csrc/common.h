@@ -32,6 +32,27 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
 }
 __device__ __forceinline__ float round_bf(float f) { return bf2f(f2bf(f)); }
 
+// four bf16 (8 bytes) <-> float4, eight bf16 (16 bytes) <-> float[8]
+__device__ __forceinline__ float4 ld_bf16x4(const bf16_t* p) {
+  const uint2 u = *(const uint2*)p;
+  return make_float4(bf2f(u.x & 0xffff), bf2f(u.x >> 16), bf2f(u.y & 0xffff), bf2f(u.y >> 16));
+}
+__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
+  return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
+}
+__device__ __forceinline__ void st_bf16x4(bf16_t* p, const float4 v) {
+  *(uint2*)p = make_uint2(pack2(v.x, v.y), pack2(v.z, v.w));
+}
+__device__ __forceinline__ void unpack8(const uint4 u, float* f) {
+  f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
+  f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
+  f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xffff0000u);
+  f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xffff0000u);
+}
+__device__ __forceinline__ uint4 pack8(const float* f) {
+  return make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
+}
+
 // Rotary pair (dims i, i + half) of one row: q·cos + rotate_half(q)·sin, or its transpose
 // (the backward).  One fused multiply-add per output with the other product rounded first —
 // written out so every kernel that rotates (rope8 / rope, the attention backward's dQ / dK
@@ -163,6 +184,9 @@ int* gemm_switch(const char* name, int* prev);  // gemm.hip: mmpt_set_switch's G
 // environment variable `off_env` (nullptr: none) is set to 0: one workgroup per work item
 int cu_slots(const char* off_env);
 int* misc_switch(const char* name, int* prev);  // misc.hip: MMPT_CE_REG
+// pointer alignment checks of the entry points (a null pointer passes)
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 }  // namespace mmpt
 
 #define MMPT_REQUIRE(cond, ...)                 \

@@ -49,12 +49,6 @@ struct DwArgs {
   int planes;                  // IDX kernels: planes in the fp32 stream (idx[b'] < planes)
 };
 
-__device__ __forceinline__ void unpack8(const uint4 u, float* f) {
-  f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
-  f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
-  f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xffff0000u);
-  f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xffff0000u);
-}
 __device__ __forceinline__ void ld8f(const float* p, float* f) {
   const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
   f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
@@ -63,12 +57,6 @@ __device__ __forceinline__ void ld8f(const float* p, float* f) {
 __device__ __forceinline__ void st8f(float* p, const float* f) {
   *(float4*)p = make_float4(f[0], f[1], f[2], f[3]);
   *(float4*)(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
-}
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
 }
 
 // Stage the pixels [y0, y0 + ph) x [x0, x0 + pw) of image b, channel groups chunk*8 .. +8, into
@@ -508,7 +496,6 @@ __global__ __launch_bounds__(256) void patchify2_kernel(long B, int H, int W, in
   }
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline unsigned blocks_for(int64_t n) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192));
 }
@@ -619,7 +606,6 @@ extern "C" int mmpt_dwconv7_bwd_weight(int64_t B, int64_t H, int64_t W, int64_t 
                (long long)B)
 #define MMPT_CN_P(what) \
   MMPT_REQUIRE(p >= 0.0 && p < 1.0, what ": p must lie in [0, 1), got %g", p)
-inline bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 
 extern "C" int mmpt_dwconv7_idx_fwd(int64_t B, int64_t Bk, int64_t H, int64_t W, int64_t C,
                                     const float* x, const void* idx, const void* w,

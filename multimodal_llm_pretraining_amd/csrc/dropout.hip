@@ -157,8 +157,6 @@ using namespace mmpt;
   MMPT_REQUIRE(h / 8 <= INT32_MAX && rows <= (INT64_MAX >> 1) / h, what ": sizes out of range"); \
   const DropArgs a = {dropout_threshold(p), dropout_scale(p), seed}
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 extern "C" int mmpt_dropout_bf16(int64_t rows, int64_t h, const void* src, int64_t ld_src,
                                  void* dst, int64_t ld_dst, double p, uint64_t seed, uint64_t site,
                                  void* stream) {
@@ -166,7 +164,7 @@ extern "C" int mmpt_dropout_bf16(int64_t rows, int64_t h, const void* src, int64
   MMPT_REQUIRE(src && dst, "dropout_bf16: null pointer");
   MMPT_REQUIRE(ld_src >= h && ld_dst >= h && ld_src % 8 == 0 && ld_dst % 8 == 0,
                "dropout_bf16: leading dims must be multiples of 8 and >= h");
-  MMPT_REQUIRE(aligned16(src) && aligned16(dst), "dropout_bf16: pointers must be 16-B aligned");
+  MMPT_REQUIRE(al16(src) && al16(dst), "dropout_bf16: pointers must be 16-B aligned");
   if (rows == 0) return MMPT_OK;
   const Launch l = plan(rows, h);
   dropout_bf16_kernel<<<l.grid, 256, 0, (hipStream_t)stream>>>(
@@ -178,7 +176,7 @@ extern "C" int mmpt_dropout_f32(int64_t rows, int64_t h, const float* src, float
                                 uint64_t seed, uint64_t site, void* stream) {
   MMPT_DROP_COMMON("dropout_f32");
   MMPT_REQUIRE(src && dst, "dropout_f32: null pointer");
-  MMPT_REQUIRE(aligned16(src) && aligned16(dst), "dropout_f32: pointers must be 16-B aligned");
+  MMPT_REQUIRE(al16(src) && al16(dst), "dropout_f32: pointers must be 16-B aligned");
   if (rows == 0) return MMPT_OK;
   const Launch l = plan(rows, h);
   dropout_f32_kernel<<<l.grid, 256, 0, (hipStream_t)stream>>>(rows, l.h8, l.wshift, src, dst, site,
@@ -194,7 +192,7 @@ extern "C" int mmpt_dropout_add_f32(int64_t rows, int64_t h, const void* y, int6
   MMPT_REQUIRE(y && resid && out, "dropout_add_f32: null pointer");
   MMPT_REQUIRE(ld_y >= h && ld_y % 8 == 0 && (!y2 || (ld_y2 >= h && ld_y2 % 8 == 0)),
                "dropout_add_f32: leading dims must be multiples of 8 and >= h");
-  MMPT_REQUIRE(aligned16(y) && aligned16(y2) && aligned16(resid) && aligned16(out),
+  MMPT_REQUIRE(al16(y) && al16(y2) && al16(resid) && al16(out),
                "dropout_add_f32: pointers must be 16-B aligned");
   if (rows == 0) return MMPT_OK;
   const Launch l = plan(rows, h);

@@ -41,18 +41,6 @@ constexpr int CV_BLOCKS = 256; // partial rows of the weight gradient at most
 constexpr int SC_CH = MMPT_SCAN_CHUNK;
 constexpr int SC_BLK = 128;    // channels per workgroup
 
-__device__ __forceinline__ void unpack8(const uint4 u, float* f) {
-  f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
-  f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
-  f[4] = __uint_as_float(u.z << 16); f[5] = __uint_as_float(u.z & 0xffff0000u);
-  f[6] = __uint_as_float(u.w << 16); f[7] = __uint_as_float(u.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
-  return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
-}
-__device__ __forceinline__ uint4 pack8(const float* f) {
-  return make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
-}
 __device__ __forceinline__ void st8f(float* p, const float* f) {
   *(float4*)p = make_float4(f[0], f[1], f[2], f[3]);
   *(float4*)(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
@@ -599,8 +587,6 @@ __global__ __launch_bounds__(256) void scan_reduce_ch_kernel(int I, int N, int n
   else ddt_bias[ch] += s;
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline bool al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
 inline int64_t up64(int64_t bytes) { return (bytes + 255) / 256 * 256; }
 
 inline bool conv_shape_ok(int64_t B, int64_t L, int64_t C) {

@@ -4,21 +4,21 @@
 // LayerNorm of RobertaLMHead, which reads a bf16 activation.  fp32 statistics, as autocast runs
 // aten::layer_norm in fp32.
 //
-// Forward kernels: one wave per row, float4 per lane, the row arithmetic of layernorm.hip's
-// ln_fwd32_kernel expression for expression (row sum, centred sum of squares, 1 / sqrt, the
-// butterfly wave_sum).  For the two entries whose row is fp32 (add_layernorm, roberta_embed)
-// hipcc emits ln_fwd32_kernel's instruction sequence per instantiation, so LN over the same
-// fp32 row gives the same bits (tests/test_roberta_gpu.py pins it); for the bf16 row of mlm_ln
-// it fuses the squares differently and rstd may move by an ulp.  Backward kernels: one
-// workgroup (256 threads) per row, grid-stride, the row arithmetic of ln_bwd_rows_kernel; the
-// per-thread dγ / dβ / bias-gradient accumulators go to [block][3][h] partials that a second
-// kernel sums in block order.  No atomics: every result is bitwise reproducible.  The dropout
+// Forward kernels: one wave per row, float4 per lane.  Each mode fills the row's registers its
+// own way (the residual add with dropout, the embedding sum, the bf16 row); the statistics and
+// the normalise are rownorm.h's, the ones layernorm.hip's ln_fwd32_kernel runs.  For the two
+// entries whose row is fp32 (add_layernorm, roberta_embed) LN over the same fp32 row gives the
+// same bits (tests/test_roberta_gpu.py pins it); for the bf16 row of mlm_ln hipcc fuses the
+// squares differently and rstd may move by an ulp.  Backward kernels: one workgroup (256
+// threads) per row, grid-stride, rownorm.h's backward row pieces; the per-thread dγ / dβ /
+// bias-gradient accumulators go to [block][3][h] partials that partials_reduce sums in block
+// order.  No atomics: every result is bitwise reproducible.  The dropout
 // masks follow K16's element numbering (philox.h): the float4 at quad q = row * h/4 + i takes the
 // four words of dropout_words(q, site, seed).
 #include <float.h>
 
-#include "common.h"
 #include "philox.h"
+#include "rownorm.h"
 
 namespace mmpt {
 namespace {
@@ -30,16 +30,6 @@ enum { PL_ADD = 0, PL_EMB = 1, PL_MLM = 2, PL_LN16 = 3, PL_EMBN = 4 };  // LN16:
 // instantiations are the code they were)
 constexpr bool pl_emb(int mode) { return mode == PL_EMB || mode == PL_EMBN; }
 
-__device__ __forceinline__ float4 ld_bf16x4(const bf16_t* p) {
-  const uint2 u = *(const uint2*)p;
-  return make_float4(bf2f(u.x & 0xffff), bf2f(u.x >> 16), bf2f(u.y & 0xffff), bf2f(u.y >> 16));
-}
-__device__ __forceinline__ void st_bf16x4(bf16_t* p, bf16_t a, bf16_t b, bf16_t c, bf16_t d) {
-  uint2 u;
-  u.x = (uint32_t)a | ((uint32_t)b << 16);
-  u.y = (uint32_t)c | ((uint32_t)d << 16);
-  *(uint2*)p = u;
-}
 // drop of one bf16 value held as a float: bf16(x * scale) (one rounding) or +0 (dropout.hip)
 __device__ __forceinline__ float drop_bf_f(float x, bool keep, float scale) {
   return keep ? round_bf(x * scale) : 0.f;
@@ -86,8 +76,8 @@ struct PlArgs {
   uint64_t nseed, nsite;
 };
 
-// Hands the compiler four plain registers: the row arithmetic below is then laid out as for a
-// row that came straight from a float4 load (ln_fwd32_kernel's), whatever produced the values.
+// Hands row_stats four plain registers, as a float4 load would, so that it compiles as it does for
+// ln_fwd32_kernel; without it EMBN at MAXJ = 8 also takes 82 VGPRs, one occupancy step down.
 __device__ __forceinline__ void opaque4(float4& v) {
   asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
 }
@@ -120,11 +110,10 @@ __global__ __launch_bounds__(256) void postln_fwd_kernel(const PlArgs a) {
     pr = (const float4*)(a.ptab + clampl(a.pos[row], a.max_pos) * h);
   }
   float4 v[MAXJ];
-  float s = 0.f;
 #pragma unroll
   for (int j = 0; j < MAXJ; ++j) {
     const int i = j * 64 + lane;
-    v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    v[j] = zero4();
     if (i < nv) {
       if (MODE == PL_ADD) {
         const float4 r = ((const float4*)(a.x32 + (long)row * h))[i];
@@ -147,19 +136,9 @@ __global__ __launch_bounds__(256) void postln_fwd_kernel(const PlArgs a) {
       }
       if (MODE != PL_ADD) opaque4(v[j]);
     }
-    s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
   }
-  const float mean = wave_sum(s) / (float)h;
-  float ss = 0.f;
-#pragma unroll
-  for (int j = 0; j < MAXJ; ++j) {
-    const int i = j * 64 + lane;
-    if (i < nv) {
-      const float c0 = v[j].x - mean, c1 = v[j].y - mean, c2 = v[j].z - mean, c3 = v[j].w - mean;
-      ss += (c0 * c0 + c1 * c1) + (c2 * c2 + c3 * c3);
-    }
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(ss) / (float)h + a.eps);
+  float mean, rstd;
+  row_stats<MAXJ, false>(v, lane, nv, h, a.eps, mean, rstd);
   if (lane == 0) {
     a.mean[row] = mean;
     a.rstd[row] = rstd;
@@ -168,9 +147,7 @@ __global__ __launch_bounds__(256) void postln_fwd_kernel(const PlArgs a) {
   for (int j = 0; j < MAXJ; ++j) {
     const int i = j * 64 + lane;
     if (i >= nv) continue;
-    const float4 g = ((const float4*)a.w)[i], bb = ((const float4*)a.b)[i];
-    float4 y = make_float4((v[j].x - mean) * rstd * g.x + bb.x, (v[j].y - mean) * rstd * g.y + bb.y,
-                           (v[j].z - mean) * rstd * g.z + bb.z, (v[j].w - mean) * rstd * g.w + bb.w);
+    float4 y = affine4(xhat4(v[j], mean, rstd), ((const float4*)a.w)[i], ((const float4*)a.b)[i]);
     if (pl_emb(MODE) && a.thr != 0) {  // h0 = dropout(y), fp32 (mmpt_dropout_f32's arithmetic)
       const philox4 k = dropout_words((uint64_t)row * nv + i, a.site, a.seed);
       y.x = k.w[0] >= a.thr ? y.x * a.scale : 0.f;
@@ -179,7 +156,7 @@ __global__ __launch_bounds__(256) void postln_fwd_kernel(const PlArgs a) {
       y.w = k.w[3] >= a.thr ? y.w * a.scale : 0.f;
     }
     if (MODE != PL_MLM) ((float4*)(a.o32 + (long)row * h))[i] = y;
-    st_bf16x4(a.o16 + (long)row * a.ld_o16 + i * 4, f2bf(y.x), f2bf(y.y), f2bf(y.z), f2bf(y.w));
+    st_bf16x4(a.o16 + (long)row * a.ld_o16 + i * 4, y);
   }
 }
 
@@ -187,14 +164,14 @@ __global__ __launch_bounds__(256) void postln_fwd_kernel(const PlArgs a) {
 template <int MODE, int PT>
 __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
   __shared__ float red[2][4][2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int h = a.h, nv = h >> 2;
   float4 aw[PT], ab[PT], aq[PT], ww[PT];
 #pragma unroll
   for (int j = 0; j < PT; ++j) {
-    aw[j] = ab[j] = aq[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    aw[j] = ab[j] = aq[j] = zero4();
     const int i = j * 256 + tid;
-    ww[j] = i < nv ? ((const float4*)a.w)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    ww[j] = i < nv ? ((const float4*)a.w)[i] : zero4();
   }
   int par = 0;
   for (int row = blockIdx.x; row < a.rows; row += gridDim.x, par ^= 1) {
@@ -209,7 +186,7 @@ __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
 #pragma unroll
     for (int j = 0; j < PT; ++j) {
       const int i = j * 256 + tid;
-      xh[j] = g1[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      xh[j] = g1[j] = zero4();
       if (i >= nv) continue;
       float4 xv, d1;
       if (MODE == PL_ADD) {
@@ -242,33 +219,19 @@ __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
         xv = ld_bf16x4(a.x16 + (long)row * a.ld_x16 + i * 4);
         d1 = ld_bf16x4(a.dy16 + (long)row * a.ld_dy16 + i * 4);
       }
-      xh[j] = make_float4((xv.x - mu) * rs, (xv.y - mu) * rs, (xv.z - mu) * rs, (xv.w - mu) * rs);
-      g1[j] = make_float4(d1.x * ww[j].x, d1.y * ww[j].y, d1.z * ww[j].z, d1.w * ww[j].w);
-      s1a += (g1[j].x * xh[j].x + g1[j].y * xh[j].y) + (g1[j].z * xh[j].z + g1[j].w * xh[j].w);
-      s1b += (g1[j].x + g1[j].y) + (g1[j].z + g1[j].w);
-      aw[j].x += d1.x * xh[j].x; aw[j].y += d1.y * xh[j].y;
-      aw[j].z += d1.z * xh[j].z; aw[j].w += d1.w * xh[j].w;
-      ab[j].x += d1.x; ab[j].y += d1.y; ab[j].z += d1.z; ab[j].w += d1.w;
+      xh[j] = xhat4(xv, mu, rs);
+      bwd_accum(xh[j], d1, ww[j], g1[j], s1a, s1b, aw[j], ab[j]);
     }
-    s1a = wave_sum(s1a);
-    s1b = wave_sum(s1b);
-    if (lane == 0) {
-      red[par][wave][0] = s1a;
-      red[par][wave][1] = s1b;
-    }
+    row_sums_put(red[par], 0, s1a, s1b);
     __syncthreads();
     const float inv_h = 1.0f / (float)h;
-    const float c1a = ((red[par][0][0] + red[par][1][0]) + (red[par][2][0] + red[par][3][0])) * inv_h;
-    const float c1b = ((red[par][0][1] + red[par][1][1]) + (red[par][2][1] + red[par][3][1])) * inv_h;
+    const float c1a = row_sum_get(red[par], 0) * inv_h, c1b = row_sum_get(red[par], 1) * inv_h;
 #pragma unroll
     for (int j = 0; j < PT; ++j) {
       const int i = j * 256 + tid;
       if (i >= nv) continue;
-      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-      o.x += rs * (g1[j].x - xh[j].x * c1a - c1b);
-      o.y += rs * (g1[j].y - xh[j].y * c1a - c1b);
-      o.z += rs * (g1[j].z - xh[j].z * c1a - c1b);
-      o.w += rs * (g1[j].w - xh[j].w * c1a - c1b);
+      float4 o = zero4();
+      dx_add(o, rs, g1[j], xh[j], c1a, c1b);
       if (MODE != PL_MLM && MODE != PL_LN16) ((float4*)(a.o32 + (long)row * h))[i] = o;
       if (pl_emb(MODE)) {  // dtype[0] = Σ_rows de in fp32: these gradients are outside autocast
         aq[j].x += o.x; aq[j].y += o.y; aq[j].z += o.z; aq[j].w += o.w;
@@ -290,7 +253,7 @@ __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
         q.z = round_bf(q.z * gelu_grad_f(pv.z));
         q.w = round_bf(q.w * gelu_grad_f(pv.w));
       }
-      st_bf16x4(a.o16 + (long)row * a.ld_o16 + i * 4, f2bf(q.x), f2bf(q.y), f2bf(q.z), f2bf(q.w));
+      st_bf16x4(a.o16 + (long)row * a.ld_o16 + i * 4, q);
       if (a.want_q2) {
         aq[j].x += q.x; aq[j].y += q.y; aq[j].z += q.z; aq[j].w += q.w;
       }
@@ -307,65 +270,32 @@ __global__ __launch_bounds__(256) void postln_bwd_kernel(const PlArgs a) {
   }
 }
 
-// Σ over blocks of partials[b][q][c] -> d0 / d1 / d2 (+=, nullable); with round2 quantity 2 is
-// rounded to bf16 first (a bias gradient: autocast's grad dtype) and also added to d2b.
-__global__ __launch_bounds__(256) void postln_reduce(int nblk, int h, const float* __restrict__ partials,
-                                                     float* d0, float* d1, float* d2, float* d2b,
-                                                     int round2) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int q = blockIdx.y, c = blockIdx.x * 64 + lane;
-  float* dst = q == 0 ? d0 : q == 1 ? d1 : d2;
-  if (dst == nullptr) return;  // uniform per workgroup
-  float s = 0.f;
-  if (c < h)
-#pragma unroll 8
-    for (int b = wave; b < nblk; b += 4) s += partials[((long)b * 3 + q) * h + c];
-  red[wave][lane] = s;
-  __syncthreads();
-  if (wave == 0 && c < h) {
-    float v = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
-    if (q == 2 && round2) {
-      v = round_bf(v);
-      if (d2b != nullptr) d2b[c] += v;
-    }
-    dst[c] += v;
-  }
-}
-
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-int pick_maxj(int64_t h) {
-  const int64_t per = (h / 4 + 63) / 64;
-  return per <= 1 ? 1 : per <= 2 ? 2 : per <= 4 ? 4 : per <= 8 ? 8 : per <= 16 ? 16 : -1;
-}
-
+// the entry points cap h at 4096, so pick_maxj / pick_pt always find an instantiation
 template <int MODE>
 int launch_fwd(const PlArgs& a, hipStream_t s, const char* what) {
   const unsigned g = (unsigned)((a.rows + PL_WAVES - 1) / PL_WAVES);
-  switch (pick_maxj(a.h)) {
-    case 1: postln_fwd_kernel<MODE, 1><<<g, 256, 0, s>>>(a); break;
-    case 2: postln_fwd_kernel<MODE, 2><<<g, 256, 0, s>>>(a); break;
-    case 4: postln_fwd_kernel<MODE, 4><<<g, 256, 0, s>>>(a); break;
-    case 8: postln_fwd_kernel<MODE, 8><<<g, 256, 0, s>>>(a); break;
-    default: postln_fwd_kernel<MODE, 16><<<g, 256, 0, s>>>(a); break;
-  }
+  dispatch_maxj(pick_maxj(a.h), [&](auto J) {
+    constexpr int MJ = decltype(J)::value == 12 ? 16 : decltype(J)::value;  // no 12 here: 16's code
+    postln_fwd_kernel<MODE, MJ><<<g, 256, 0, s>>>(a);
+  });
   return check_launch(what);
 }
 
+// d0 / d1 / d2 (+=, nullable) take Σ dγ, Σ dβ and quantity 2; with round2 quantity 2 is a bias
+// gradient: rounded to bf16 and also added to d2b
 template <int MODE>
 int launch_bwd(const PlArgs& a, float* d0, float* d1, float* d2, float* d2b, int round2,
                hipStream_t s, const char* what) {
   const int nblk = (int)std::min<int64_t>(PL_BLOCKS, a.rows);
-  const int64_t per = (a.h / 4 + 255) / 256;
-  if (per <= 1) postln_bwd_kernel<MODE, 1><<<nblk, 256, 0, s>>>(a);
-  else if (per <= 2) postln_bwd_kernel<MODE, 2><<<nblk, 256, 0, s>>>(a);
-  else postln_bwd_kernel<MODE, 4><<<nblk, 256, 0, s>>>(a);
+  dispatch_pt(pick_pt(a.h), [&](auto PT) {
+    postln_bwd_kernel<MODE, decltype(PT)::value><<<nblk, 256, 0, s>>>(a);
+  });
   int rc = check_launch(what);
   if (rc) return rc;
   if (d0 == nullptr && d1 == nullptr && d2 == nullptr) return rc;
   dim3 rg((unsigned)((a.h + 63) / 64), 3u);
-  postln_reduce<<<rg, 256, 0, s>>>(nblk, a.h, a.partials, d0, d1, d2, d2b, round2);
+  partials_reduce<<<rg, 256, 0, s>>>(nblk, a.h, 3, a.partials, d0, d1, d2, nullptr, nullptr,
+                                     round2 ? 2 : -1, d2b);
   return check_launch(what);
 }
 

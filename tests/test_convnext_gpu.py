@@ -197,8 +197,8 @@ def test_layerscale(K, rows, C):
 
 
 # ------------------------------------------------------------------ ln16_bwd
-@pytest.mark.parametrize("h", (24, 72, 192, 1032))
-@pytest.mark.parametrize("rows", (1, 3, 257))
+@pytest.mark.parametrize("rows,h", [(r, h) for r in (1, 3, 257) for h in (24, 72, 192, 1032)]
+                         + [(5, 512), (5, 520), (129, 3072), (5, 4096), (1029, 64)])
 def test_ln16_bwd(K, rows, h):
     g = torch.Generator().manual_seed(7919 * rows + 31 * h + 21)
     c = strided(torch.randn(rows, h, generator=g).to(BF16).cuda())

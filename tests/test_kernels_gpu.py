@@ -132,10 +132,14 @@ def test_gemm_quick_gelu_epilogues(K, M, N):
     assert relerr(db, dg.float().sum(0).to(torch.bfloat16).float()) < 2e-3  # bf16 grad_bias
 
 
-def test_layernorm_f32(K):
+NORM_SHAPES = [(5, 512), (5, 520), (129, 3072), (5, 4096), (1029, 64)]  # every MAXJ / PT, masked lanes
+
+
+@pytest.mark.parametrize("rows,h", [(577 * 3, 1024)] + NORM_SHAPES)
+def test_layernorm_f32(K, rows, h):
     """fp32-output LayerNorm (CLIP pre_layrnorm) fwd/bwd vs torch fp32."""
     torch.manual_seed(6)
-    rows, h, eps = 577 * 3, 1024, 1e-5
+    eps = 1e-5
     x = torch.randn(rows, h, device=dev) * 2 + 0.5
     w = torch.randn(h, device=dev)
     b = torch.randn(h, device=dev)
@@ -749,7 +753,8 @@ def test_gemm_rejects_bad_args(K):
 
 
 # ------------------------------------------------------------------ LayerNorm
-@pytest.mark.parametrize("rows,h,eps", [(129, 2048, 1e-5), (77, 768, 1e-12), (5, 64, 1e-5)])
+@pytest.mark.parametrize("rows,h,eps", [(129, 2048, 1e-5), (77, 768, 1e-12), (5, 64, 1e-5)]
+                         + [(r, h, 1e-5) for r, h in NORM_SHAPES])
 def test_layernorm_dual(K, rows, h, eps):
     torch.manual_seed(2)
     x = torch.randn(rows, h, device=dev) * 2 + 0.5
@@ -775,6 +780,19 @@ def test_layernorm_dual(K, rows, h, eps):
     assert relerr(dx, xr.grad + dres) < 1e-4
     for a, r in ((dw1, w1r), (db1, b1r), (dw2, w2r), (db2, b2r)):
         assert relerr(a, r.grad) < 1e-4
+    # the wave-per-row entry (no Python wrapper): the same bound
+    from multimodal_llm_pretraining_amd import _lib
+    ws = torch.empty(_lib.query("mmpt_layernorm_bwd_workspace_bytes", rows, h), device=dev,
+                     dtype=torch.uint8)
+    dxw = torch.empty(rows, h, device=dev)
+    gw = [torch.zeros(h, device=dev) for _ in range(4)]
+    _lib.call("mmpt_layernorm_bwd", rows, h, x.data_ptr(), h, mean.data_ptr(), rstd.data_ptr(),
+              dy1.data_ptr(), w1.data_ptr(), dy2.data_ptr(), w2.data_ptr(), dres.data_ptr(),
+              dxw.data_ptr(), *(t.data_ptr() for t in gw), ws.data_ptr(),
+              torch.cuda.current_stream().cuda_stream)
+    assert relerr(dxw, xr.grad + dres) < 1e-4
+    for a, r in zip(gw, (w1r, b1r, w2r, b2r)):
+        assert relerr(a, r.grad) < 1e-4
     # fused outputs: bf16 copy of dx and the bias gradient Σ_rows bf16(dx) (rounded to
     # bf16, accumulated into two fp32 targets); the single-LN form (ViT) too
     dxb = torch.empty(rows, h, device=dev, dtype=torch.bfloat16)
@@ -792,7 +810,7 @@ def test_layernorm_dual(K, rows, h, eps):
 @pytest.mark.parametrize("rows,h,dual", [(9001, 2048, True), (5003, 768, False), (4100, 64, True)])
 def test_layernorm_fwd_persistent_bitwise(K, rows, h, dual):
     """Round 5: above 4096 rows the forward runs persistent workgroups with γ / β staged in LDS
-    (ln_fwd_persist_kernel); its rows are bitwise the per-row kernel's (which a 4096-row call
+    (ln_fwd_kernel's PERSIST form); its rows are bitwise the per-row kernel's (which a 4096-row call
     of the same first rows runs), statistics included, one LN or two."""
     torch.manual_seed(rows)
     x = torch.randn(rows, h, device=dev) * 2 + 0.5
@@ -1315,7 +1333,7 @@ def test_clip_coef(K):
 
 
 # ------------------------------------------------------------------ Llama side (K17)
-@pytest.mark.parametrize("rows,h", [(3000, 2048), (37, 256)])
+@pytest.mark.parametrize("rows,h", [(3000, 2048), (37, 256)] + NORM_SHAPES)
 def test_rmsnorm(K, rows, h):
     """LlamaRMSNorm fwd (fp32 stats, w * x̂ -> bf16) and bwd (dx with residual add + bf16
     copy, dw) vs torch fp32 autograd of HF's formula."""

@@ -39,6 +39,9 @@ EPS = 1e-5
 SEED, SITE = 0x1234ABCD5, (7 << 32) | (3 << 4) | 1
 ROWS, HS, PS = (1, 3, 257), (72, 128, 1024, 1032), (0.0, 0.1)
 B, S = 4, 48  # the engine tests' batch (σ is measured at this shape)
+# the kernel tests' (rows, h): ROWS x HS, then widths that reach MAXJ = 2, 12, 16 / PT = 2, 4 of the
+# row kernels, masked lanes in the last vector (520) and more rows than backward workgroups (1029)
+SHAPES = [(r, h) for r in ROWS for h in HS] + [(5, 512), (5, 520), (129, 3072), (5, 4096), (1029, 64)]
 
 
 @pytest.fixture(scope="module")
@@ -134,8 +137,7 @@ def params(h, g):
 
 # ------------------------------------------------------------------ add_layernorm_fwd
 @pytest.mark.parametrize("p", PS)
-@pytest.mark.parametrize("h", HS)
-@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("rows,h", SHAPES)
 def test_add_layernorm_fwd(K, rows, h, p):
     g = gen(rows, h, 1)
     resid = (torch.randn(rows, h, generator=g) * 2 + 0.5).cuda()
@@ -179,8 +181,7 @@ def existing_bwd(K, x, mean, rstd, dyb, w, start):
 
 
 @pytest.mark.parametrize("mode", ["dyb", "dy32", "both"])
-@pytest.mark.parametrize("h", HS)
-@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("rows,h", SHAPES)
 def test_add_layernorm_bwd(K, rows, h, mode):
     g = gen(rows, h, 2)
     s = (torch.randn(rows, h, generator=g) * 2 + 0.5).cuda()
@@ -247,8 +248,7 @@ def gelu_grad64(x):
     return 0.5 * (1 + torch.erf(x / math.sqrt(2))) + x * torch.exp(-x * x / 2) / math.sqrt(2 * math.pi)
 
 
-@pytest.mark.parametrize("h", HS)
-@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("rows,h", SHAPES)
 def test_mlm_ln(K, rows, h):
     g = gen(rows, h, 3)
     gl = strided(torch.randn(rows, h, generator=g).to(BF16).cuda())

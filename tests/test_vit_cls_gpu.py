@@ -53,6 +53,9 @@ def _cls_rows(t, batch, tokens):
 
 
 SHAPES = [(b, t, h) for b in (1, 3, 65) for t in (1, 2, 17, 197) for h in (72, 128, 1024)]
+# widths that reach MAXJ = 2, 12, 16 / PT = 2, 4, masked lanes in the last vector (520), and more
+# CLS rows than backward workgroups (1029)
+SHAPES += [(5, 2, 512), (5, 2, 520), (129, 2, 3072), (5, 2, 4096), (1029, 2, 64)]
 
 
 @pytest.mark.parametrize("batch,tokens,h", SHAPES)

@@ -1060,6 +1060,13 @@ __device__ __forceinline__ void epilogue4w(const GemmParams& p, v4f (&acc)[8][8]
 #ifndef MMPT_GEMM_STG_RELAX  // (diagnostic) bit 0: loop-top wait, bit 1: first K-tile waits
 #define MMPT_GEMM_STG_RELAX 3
 #endif
+// KRP: the K_ROWS x K_ROWS forms (the weight gradients) run their K-tiles in pairs with the
+// buffer parity a compile-time constant, the images ordered [A0 A1 B0 B1], every transposed
+// read "per-lane register + immediate" and every DMA piece's M0 "scalar + literal" (gemm4p_body;
+// profiles/wgrad_loop/).  0 builds the one-K-tile loop with the run-time parity for A/Bs.
+#ifndef MMPT_GEMM_KR_PAR
+#define MMPT_GEMM_KR_PAR 1
+#endif
 #ifndef MMPT_GEMM_4P_NT
 #define MMPT_GEMM_4P_NT 1  // nontemporal stores for the plain / dGELU outputs too: lm_head fwd +3%,
                            // qkv fwd +1.6%, 8192^3 +3% (profiles/r04/epi2/); 0 for A/B builds
@@ -1465,6 +1472,12 @@ __device__ __forceinline__ void dma_m0(v4i_t srd, uint32_t voff, uint32_t m0) {
   asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
                :: "v"(voff), "s"(srd), "s"(m0) : "memory");
 }
+// the same with M0 = `base` + the compile-time LIT in one scalar instruction (KRP)
+template <int LIT>
+__device__ __forceinline__ void dma_m0_lit(v4i_t srd, uint32_t voff, uint32_t base) {
+  asm volatile("s_add_u32 m0, %2, %3\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds"
+               :: "v"(voff), "s"(srd), "s"(base), "n"(LIT) : "memory", "scc");
+}
 template <int N>
 __device__ __forceinline__ void vm_wait_n() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -1481,6 +1494,13 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
   constexpr int EPI = epi_base<EPI_>();
   constexpr int IMG = 256 * BK * 2;  // 32 KiB: one operand's K-tile image (two 128-row halves)
   constexpr bool USE_LUT = lut4<EPI_>();
+  // KRP (MMPT_GEMM_KR_PAR): see ktile / `range` below
+  constexpr bool KRP = MMPT_GEMM_KR_PAR && !MMPT_GEMM_STG && LA == MMPT_K_ROWS && LB == MMPT_K_ROWS;
+  // byte offset of operand op's (0 = A, 1 = B) image of buffer buf: [A0 B0 A1 B1], or (KRP)
+  // [A0 A1 B0 B1] — both buffers of an operand within the 16-bit offset field of one ds_read
+  constexpr auto img_off = [](int op, int buf) constexpr -> int {
+    return (KRP ? 2 * op + buf : 2 * buf + op) * IMG;
+  };
   // STG (round 5): the fast plain epilogue stages its output
   // rows in the LDS left free beside the two K-tile buffers (4 waves x 8 KiB), not in buffer 1,
   // so the next tile's K-tile-1 A pieces go out BEFORE the epilogue's stores and its first
@@ -1547,6 +1567,15 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
     else return (4 * wave + (q & 3)) * 4 + (lane >> 4);
   };
   uint32_t ktA = 0, ktB = 0;
+  // KRP: the resource bases of K-tile t + 2 (the one the loop stages), advanced by one 64-bit
+  // scalar add per operand and K-tile instead of a 32 x 64-bit product per piece
+  const bf16_t *An = nullptr, *Bn = nullptr;
+  long stepA = 0, stepB = 0;
+  auto uniform_ptr = [](const bf16_t* q) -> const bf16_t* {
+    const uintptr_t b = (uintptr_t)q;
+    return (const bf16_t*)((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b) |
+                           ((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32)) << 32));
+  };
   auto offsets = [&](const TileCoord& c, int ord) {
     if constexpr (EPI == EPI_SPLIT) {
       kbeg = c.split * p.kchunk;
@@ -1567,8 +1596,14 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
     const int k0 = kbeg + (kdir < 0 ? (nk - 1) * BK : 0);  // the first K-tile walked
     Ab = LA == MMPT_ROWS_K ? p.A + (long)c.m0 * p.lda + k0 : p.A + (long)k0 * p.lda;
     Bb = LB == MMPT_ROWS_K ? p.B + (long)c.n0 * p.ldb + k0 : p.B + (long)k0 * p.ldb;
+    if constexpr (KRP) {
+      stepA = (long)(kdir * BK) * p.lda;
+      stepB = (long)(kdir * BK) * p.ldb;
+      An = uniform_ptr(Ab + 2 * stepA);
+      Bn = uniform_ptr(Bb + 2 * stepB);
+    }
   };
-  char* const imgA0 = smem;            // buffer b: A at smem + 2b*IMG, B at smem + (2b+1)*IMG
+  char* const imgA0 = smem;            // operand images: img_off
   // LDS byte address of the image base (M0 of the DMA), as a 32-bit scalar: the per-piece M0
   // is then one scalar add (a generic LDS pointer costs a 64-bit add + null test)
   const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)LDS_PTR(char, smem));
@@ -1590,37 +1625,83 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
     t *= kdir;
     const bf16_t* base = LA == MMPT_ROWS_K ? Ab + t * BK : Ab + (long)t * BK * p.lda;
     dma_m0(buf_rsrc4(base), vo,
-           lds0 + (uint32_t)((2 * buf) * IMG) + piece_lds(std::integral_constant<int, LA>{}, q));
+           lds0 + (uint32_t)img_off(0, buf) + piece_lds(std::integral_constant<int, LA>{}, q));
   };
   auto dmaB = [&](int buf, int t, int q) {
     const uint32_t vo = kt_off(ktB, t, q, vb[q]);
     t *= kdir;
     const bf16_t* base = LB == MMPT_ROWS_K ? Bb + t * BK : Bb + (long)t * BK * p.ldb;
     dma_m0(buf_rsrc4(base), vo,
-           lds0 + (uint32_t)((2 * buf + 1) * IMG) + piece_lds(std::integral_constant<int, LB>{}, q));
+           lds0 + (uint32_t)img_off(1, buf) + piece_lds(std::integral_constant<int, LB>{}, q));
+  };
+  // KRP: piece Q of K-tile t (= the loop's t + 2) into buffer BUF of operand OP, from the
+  // running base; M0 = this wave's piece 0 of the operand's buffer 0 + a literal
+  const uint32_t ldsA = lds0 + (uint32_t)img_off(0, 0) + (uint32_t)(4 * wave * 1024);
+  const uint32_t ldsB = lds0 + (uint32_t)img_off(1, 0) + (uint32_t)(4 * wave * 1024);
+  auto dma_next = [&](auto op_c, auto buf_c, auto q_c, int t) {
+    constexpr int OP = decltype(op_c)::value, BUF = decltype(buf_c)::value, Q = decltype(q_c)::value;
+    constexpr int LIT = img_off(OP, BUF) - img_off(OP, 0) + (Q >> 2) * 16384 + (Q & 3) * 1024;
+    if constexpr (OP == 0) dma_m0_lit<LIT>(buf_rsrc4(An), kt_off(ktA, t, Q, va[Q]), ldsA);
+    else dma_m0_lit<LIT>(buf_rsrc4(Bn), kt_off(ktB, t, Q, vb[Q]), ldsB);
   };
   // prologue DMA of a tile: K-tiles 0 and 1 (B pieces first, as in the loop)
+  // buf0(): the buffer of the tile's K-tile 0 (K-tile t lives in buffer (t + buf0()) & 1) — 0,
+  // or (KRP) nk & 1, so that the tile's last two K-tiles lie in buffers 0 and 1 whatever nk is
+  // and each runs as ONE instance (a two-way choice there made hipcc rotate the accumulators
+  // through ~220 v_accvgpr_mov per K-tile of the main loop and spill)
+  auto buf0 = [&]() -> int { return KRP ? (nk & 1) : 0; };
   auto prologue = [&]() {
+    const int s0 = buf0();
 #pragma unroll
-    for (int q = 0; q < 8; ++q) dmaB(0, 0, q);
+    for (int q = 0; q < 8; ++q) dmaB(s0, 0, q);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) dmaA(0, 0, q);
+    for (int q = 0; q < 8; ++q) dmaA(s0, 0, q);
     if (nk > 1) {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) dmaB(1, 1, q);
+      for (int q = 0; q < 8; ++q) dmaB(s0 ^ 1, 1, q);
 #pragma unroll
-      for (int q = 0; q < 8; ++q) dmaA(1, 1, q);
+      for (int q = 0; q < 8; ++q) dmaA(s0 ^ 1, 1, q);
     }
   };
   // fragments: rows 16i + (lane & 15) of the wave's 128-row half, k-half s (frag)
+  // KRP: frag<MMPT_K_ROWS>'s address is (8g + q)·RB + 32·(i ^ sw) + 16·(p >> 1) + 8·(p & 1) per
+  // lane (g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3, sw = q | (g & 1) << 2: the chunk
+  // swizzle meets the fragment index under an XOR) + 8192·s + the image — so one per-lane
+  // LDS address per fragment index and operand (ra / rb: buffer 0, k-half 0; set per tile by
+  // frag_addrs, opaque to hipcc) and the k-half, the buffer and the second read (+4·RB) in the
+  // ds_read offset field
+  uint32_t ra[8], rb[8];
+  auto frag_addrs = [&]() {
+    if constexpr (KRP) {
+      const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3, sw = q | ((g & 1) << 2);
+      const uint32_t ln = lds0 + (uint32_t)((8 * g + q) * 256 + (pp >> 1) * 16 + (pp & 1) * 8);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        ra[i] = ln + (uint32_t)(img_off(0, 0) + wm * 16384 + (i ^ sw) * 32);
+        if constexpr (swiglu_map<EPI_>())
+          rb[i] = ln + (uint32_t)(img_off(1, 0) + (i >> 2) * 16384 + ((wn * 4 + (i & 3)) ^ sw) * 32);
+        else
+          rb[i] = ln + (uint32_t)(img_off(1, 0) + wn * 16384 + (i ^ sw) * 32);
+        asm volatile("" : "+v"(ra[i]));
+        asm volatile("" : "+v"(rb[i]));
+      }
+    }
+  };
+  auto rd_krp = [&](uint32_t base, int off) -> v8s {
+    const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(v4s, (uintptr_t)(base + (uint32_t)off)));
+    const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(v4s, (uintptr_t)(base + (uint32_t)(off + 1024))));
+    return v8s{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  };
   auto rdA = [&](int buf, int s, int i) -> v8s {
-    return frag<LA, 128>(imgA0 + (2 * buf) * IMG + wm * 16384, 16 * i, s, lane);
+    if constexpr (KRP) return rd_krp(ra[i], buf * IMG + s * 8192);
+    else return frag<LA, 128>(imgA0 + img_off(0, buf) + wm * 16384, 16 * i, s, lane);
   };
   auto rdB = [&](int buf, int s, int j) -> v8s {
-    if constexpr (swiglu_map<EPI_>())  // gate tiles j < 4, their up tiles j >= 4 (see swiglu_map)
-      return frag<LB, 128>(imgA0 + (2 * buf + 1) * IMG + (j >> 2) * 16384, wn * 64 + 16 * (j & 3),
+    if constexpr (KRP) return rd_krp(rb[j], buf * IMG + s * 8192);
+    else if constexpr (swiglu_map<EPI_>())  // gate tiles j < 4, their up tiles j >= 4 (see swiglu_map)
+      return frag<LB, 128>(imgA0 + img_off(1, buf) + (j >> 2) * 16384, wn * 64 + 16 * (j & 3),
                            s, lane);
-    return frag<LB, 128>(imgA0 + (2 * buf + 1) * IMG + wn * 16384, 16 * j, s, lane);
+    else return frag<LB, 128>(imgA0 + img_off(1, buf) + wn * 16384, 16 * j, s, lane);
   };
   v8s a[2][8], b[2][8];
   v4f acc[8][8];
@@ -1639,12 +1720,25 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
   // srcC = 0 instead of reading the accumulators
   // CS (CSA kernels): 0 = no row sums in this K-tile; 1 = sum every A fragment; 2 = the same
   // with the runtime weight cs_w (1 or 0: one instance for the tile's last two K-tiles)
-  auto ktile = [&](int t, auto dma_c, auto nxt_c, auto xs_c, auto z_c, auto cs_c) {
+  // PAR: the buffer that holds K-tile t as a constant (KRP), or -1 = t & 1 at run time
+  auto ktile = [&](int t, auto par_c, auto dma_c, auto nxt_c, auto xs_c, auto z_c, auto cs_c) {
+    constexpr int PAR = decltype(par_c)::value;
     constexpr bool DMA = decltype(dma_c)::value, NXT = decltype(nxt_c)::value;
     constexpr int CS = decltype(cs_c)::value;
     constexpr int XS = decltype(xs_c)::value;
     constexpr bool Z = decltype(z_c)::value;
-    const int X = t & 1, Y = X ^ 1;
+    static_assert(KRP == (PAR >= 0), "constant parity: the KRP forms, and only they");
+    const int X = PAR < 0 ? (t & 1) : PAR, Y = X ^ 1;
+    auto dmaAn = [&](auto q_c) {  // piece q of K-tile t + 2 into the buffer this K-tile releases
+      if constexpr (KRP)
+        dma_next(std::integral_constant<int, 0>{}, std::integral_constant<int, (PAR > 0)>{}, q_c, t + 2);
+      else dmaA(X, t + 2, decltype(q_c)::value);
+    };
+    auto dmaBn = [&](auto q_c) {
+      if constexpr (KRP)
+        dma_next(std::integral_constant<int, 1>{}, std::integral_constant<int, (PAR > 0)>{}, q_c, t + 2);
+      else dmaB(X, t + 2, decltype(q_c)::value);
+    };
 #define G4_STEP(U)                                                                            \
   {                                                                                           \
     constexpr int s_ = (U) >> 6, i_ = ((U)&63) >> 3, j_ = (U)&7;                              \
@@ -1657,19 +1751,19 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
       lgkm_wait0();                                                                           \
       __builtin_amdgcn_s_barrier();                                                           \
     }                                                                                         \
-    if constexpr (DMA && (U) >= 21 && (U) < 53 && (((U)-21) & 3) == 0) dmaB(X, t + 2, ((U)-21) >> 2); \
+    if constexpr (DMA && (U) >= 21 && (U) < 53 && (((U)-21) & 3) == 0) dmaBn(std::integral_constant<int, (((U)-21) >> 2) & 7>{}); \
     if constexpr ((U) >= 22 && (U) < 54 && (((U)-22) & 3) == 0) a[1][((U)-22) >> 2] = rdA(X, 1, ((U)-22) >> 2); \
     if constexpr ((U) == 55 && DMA) {                                                         \
       lgkm_wait0();                                                                           \
       __builtin_amdgcn_s_barrier();                                                           \
     }                                                                                         \
-    if constexpr (DMA && (U) >= 56 && (U) < 72 && (((U)-56) & 3) == 0) dmaA(X, t + 2, ((U)-56) >> 2); \
+    if constexpr (DMA && (U) >= 56 && (U) < 72 && (((U)-56) & 3) == 0) dmaAn(std::integral_constant<int, (((U)-56) >> 2) & 7>{}); \
     if constexpr ((U) == 71 && NXT) { /* B(t+1) landed */                                     \
       vm_wait_n<((DMA ? 20 : 8) + XS < 63 ? (DMA ? 20 : 8) + XS : 63)>();                   \
       __builtin_amdgcn_s_barrier();                                                           \
     }                                                                                         \
     if constexpr (NXT && (U) >= 72 && (U) < 104 && (((U)-72) & 3) == 1) b[0][((U)-72) >> 2] = rdB(Y, 0, ((U)-72) >> 2); \
-    if constexpr (DMA && (U) >= 74 && (U) < 106 && (((U)-74) & 7) == 0) dmaA(X, t + 2, 4 + (((U)-74) >> 3)); \
+    if constexpr (DMA && (U) >= 74 && (U) < 106 && (((U)-74) & 7) == 0) dmaAn(std::integral_constant<int, (4 + (((U)-74) >> 3)) & 7>{}); \
     if constexpr ((U) == 107 && NXT) { /* A(t+1) landed */                                    \
       vm_wait_n<((DMA ? 16 : 0) + XS < 63 ? (DMA ? 16 : 0) + XS : 63)>();                   \
       __builtin_amdgcn_s_barrier();                                                           \
@@ -1682,6 +1776,10 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
 #undef G4_S16
 #undef G4_S4
 #undef G4_STEP
+    if constexpr (KRP && DMA) {
+      An += stepA;
+      Bn += stepB;
+    }
   };
   using T_ = std::true_type;
   using F_ = std::false_type;
@@ -1693,6 +1791,26 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
   // choosing the K-tile instance by a branch per K-tile spilled ~1200 VGPRs.
   using C1 = std::integral_constant<int, CSA ? 1 : 0>;
   using C2 = std::integral_constant<int, CSA ? 2 : 0>;
+  // KRP: a K-tile instance per buffer.  A range [t, e) of K-tiles runs as pairs (buffer 0,
+  // buffer 1) with a start in buffer 1 and an end in buffer 0 peeled, so no K-tile chooses its
+  // instance by a branch of its own; the two peeled last K-tiles are in buffers 0 and 1 (buf0).
+  using P0 = std::integral_constant<int, KRP ? 0 : -1>;
+  using P1 = std::integral_constant<int, KRP ? 1 : -1>;
+  using X0 = std::integral_constant<int, 0>;
+  auto range = [&](int& t, int e, auto cs_c) {
+    if (t < e && ((t + buf0()) & 1)) {
+      ktile(t, P1{}, T_{}, T_{}, X0{}, F_{}, cs_c);
+      ++t;
+    }
+    for (; t + 1 < e; t += 2) {
+      ktile(t, P0{}, T_{}, T_{}, X0{}, F_{}, cs_c);
+      ktile(t + 1, P1{}, T_{}, T_{}, X0{}, F_{}, cs_c);
+    }
+    if (t < e) {
+      ktile(t, P0{}, T_{}, T_{}, X0{}, F_{}, cs_c);
+      ++t;
+    }
+  };
   offsets(tc, 0);
   prologue();
   // VM instructions the previous tile's epilogue issued AFTER this tile's prologue DMA, at
@@ -1727,10 +1845,11 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
       vm_wait_n<0>();
     }
     __builtin_amdgcn_s_barrier();
+    frag_addrs();
 #pragma unroll
-    for (int i = 0; i < 8; ++i) a[0][i] = rdA(0, 0, i);
+    for (int i = 0; i < 8; ++i) a[0][i] = rdA(buf0(), 0, i);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) b[0][j] = rdB(0, 0, j);
+    for (int j = 0; j < 8; ++j) b[0][j] = rdB(buf0(), 0, j);
     if constexpr (CSA) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) cs[i] = 0.f;
@@ -1739,7 +1858,6 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
       cs_hi = (int)((long)nm * (col + 1) / p.tiles_n);
       cs_w = col == p.tiles_n - 1 ? 0x3f803f80u : 0u;
     }
-    using X0 = std::integral_constant<int, 0>;
     using XE = std::integral_constant<int, epi4_fast_vm<EPI_>()>;
     int t0 = 0;
     if constexpr (STG) {
@@ -1748,13 +1866,13 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
       // the VALU-write -> MFMA-srcC wait states — the MFMAs are inline asm, invisible to its
       // hazard recognizer — and gave wrong tiles.)
       if ((MMPT_GEMM_STG_RELAX & 2) && relax && nk > 2) {  // the previous stores in flight
-        ktile(0, T_{}, T_{}, XE{}, T_{}, C0{});
+        ktile(0, P0{}, T_{}, T_{}, XE{}, T_{}, C0{});
       } else if ((MMPT_GEMM_STG_RELAX & 2) && relax && nk == 2) {
-        ktile(0, F_{}, T_{}, XE{}, T_{}, C0{});
+        ktile(0, P0{}, F_{}, T_{}, XE{}, T_{}, C0{});
       } else if (nk > 2) {
-        ktile(0, T_{}, T_{}, X0{}, T_{}, C0{});
+        ktile(0, P0{}, T_{}, T_{}, X0{}, T_{}, C0{});
       } else if (nk == 2) {
-        ktile(0, F_{}, T_{}, X0{}, T_{}, C0{});
+        ktile(0, P0{}, F_{}, T_{}, X0{}, T_{}, C0{});
       }
       t0 = nk >= 2 ? 1 : 0;
     } else {
@@ -1762,16 +1880,38 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
       for (int i = 0; i < 8; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+      if constexpr (KRP) {
+        // the zeroing stays HERE: hipcc sank it into the peeled first K-tile, next to the
+        // MFMAs that read the accumulators (the hazard of the STG note above; wrong sums at
+        // odd K-tile counts).  Volatile statements keep their order; then the wait states.
+        // This is checked, not guaranteed: nothing forbids hipcc a copy of an accumulator
+        // between the fence and the first MFMA, which its hazard recognizer would not see
+        // (today's build has none: no v_accvgpr_write near an MFMA in the assembly, and
+        // tests/test_gemm_wgrad_loop_gpu.py is exact at every K-tile count).  A first K-tile
+        // instance with srcC = 0 (Z, as STG has) would need no zeroing at all.
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) asm volatile("" : "+a"(acc[i][j]));
+        asm volatile("s_nop 3");
+      }
     }
-    if constexpr (CSA) {
+    if constexpr (KRP) {
       int t = t0;
-      for (; t < cs_lo; ++t) ktile(t, T_{}, T_{}, X0{}, F_{}, C0{});
-      for (; t < cs_hi; ++t) ktile(t, T_{}, T_{}, X0{}, F_{}, C1{});
-      for (; t + 2 < nk; ++t) ktile(t, T_{}, T_{}, X0{}, F_{}, C0{});
+      if constexpr (CSA) {
+        range(t, cs_lo, C0{});
+        range(t, cs_hi, C1{});
+      }
+      range(t, nk - 2, C0{});
+    } else if constexpr (CSA) {
+      int t = t0;
+      for (; t < cs_lo; ++t) ktile(t, P0{}, T_{}, T_{}, X0{}, F_{}, C0{});
+      for (; t < cs_hi; ++t) ktile(t, P0{}, T_{}, T_{}, X0{}, F_{}, C1{});
+      for (; t + 2 < nk; ++t) ktile(t, P0{}, T_{}, T_{}, X0{}, F_{}, C0{});
     } else {
-      for (int t = t0; t + 2 < nk; ++t) ktile(t, T_{}, T_{}, X0{}, F_{}, C0{});
+      for (int t = t0; t + 2 < nk; ++t) ktile(t, P0{}, T_{}, T_{}, X0{}, F_{}, C0{});
     }
-    if (nk >= 2 && nk - 2 >= t0) ktile(nk - 2, F_{}, T_{}, X0{}, F_{}, C2{});
+    if (nk >= 2 && nk - 2 >= t0) ktile(nk - 2, P0{}, F_{}, T_{}, X0{}, F_{}, C2{});
     // the fast epilogue's operands load under the last K-tile (no LDS-DMA is in flight there)
     const bool fast = FAST;  // (the launch guarantees its alignment / N % 8 conditions)
     uint4 qb[4], qa[3][4], qu[3][4], qra[2][4];
@@ -1814,8 +1954,8 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
         }
       }
     }
-    if (STG && nk == 1) ktile(0, F_{}, F_{}, X0{}, std::integral_constant<bool, STG>{}, C0{});
-    else ktile(nk - 1, F_{}, F_{}, X0{}, F_{}, C2{});
+    if (STG && nk == 1) ktile(0, P0{}, F_{}, F_{}, X0{}, std::integral_constant<bool, STG>{}, C0{});
+    else ktile(nk - 1, P1{}, F_{}, F_{}, X0{}, F_{}, C2{});
     if constexpr (FAST) {
       // wait for those loads HERE, before the next tile's DMA: hipcc does not see the asm
       // LDS-DMA, and its wait at their first use would drain the DMA as well
@@ -1853,32 +1993,35 @@ __device__ __forceinline__ void gemm4p_body(const GemmParams& p) {
     w = work_id(nwg, it);
     if constexpr (FAST) {
       lgkm_wait0();
-      __builtin_amdgcn_s_barrier();  // buffer 1 (the staging area) is free
+      __builtin_amdgcn_s_barrier();  // the staging area (K-tile 1's A image) is free
       if (w >= 0) {
         tc = coord_of(p, w, 256, 256);
         offsets(tc, it);
+        const int s0 = buf0();
 #pragma unroll
-        for (int q = 0; q < 8; ++q) dmaB(0, 0, q);
+        for (int q = 0; q < 8; ++q) dmaB(s0, 0, q);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) dmaA(0, 0, q);
+        for (int q = 0; q < 8; ++q) dmaA(s0, 0, q);
         if (nk > 1) {
 #pragma unroll
-          for (int q = 0; q < 8; ++q) dmaB(1, 1, q);
+          for (int q = 0; q < 8; ++q) dmaB(s0 ^ 1, 1, q);
           if constexpr (STG) {
 #pragma unroll
-            for (int q = 0; q < 8; ++q) dmaA(1, 1, q);
+            for (int q = 0; q < 8; ++q) dmaA(s0 ^ 1, 1, q);
           }
         }
       }
+      // (the A image of the next tile's K-tile 1 — its DMA is issued below, after the staging
+      // reads; after the last tile every image is free)
       epilogue4f<EPI_>(p, acc, cur.m0, cur.n0, lane, wm, wn, lut,
-                       smem + (STG ? 4 : 2) * IMG + wave * 8192, qb, qa, qu, qra, qrc);
+                       smem + (STG ? 4 * IMG : img_off(0, buf0() ^ 1)) + wave * 8192, qb, qa, qu, qra, qrc);
       if (w < 0) break;
       if constexpr (!STG) {
         if (nk > 1) {
           lgkm_wait0();
           __builtin_amdgcn_s_barrier();  // every wave's staging reads are done
 #pragma unroll
-          for (int q = 0; q < 8; ++q) dmaA(1, 1, q);
+          for (int q = 0; q < 8; ++q) dmaA(buf0() ^ 1, 1, q);
         }
       }
       // whole tiles issue every store (the count the next wait leaves in flight); an edge tile
